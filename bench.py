@@ -10,6 +10,10 @@ protocol on the native gfx950 kernels, reduce-scatter of gradients (ZeRO-1 shard
 folded L2 regularizers) on the shard, all-gather of bf16 weights. Batch 256 per GPU (weak scaling),
 synthetic ImageNet-shaped data and random-init weights (no datasets / checkpoints are available offline).
 Rank 0 prints ONE JSON line; value = whole-job images/sec; the time is the MAX over ranks.
+
+A plain run sets up, warms up (which includes the short graph-or-eager trial that picks the faster launch mode),
+times the K steps and prints the line. ``--dump-outputs DIR`` also writes the last timed step's loss and a seeded
+sample of the updated weights as DIR/*.npy; ``--full`` is where measurements beyond the headline figure go.
 """
 import argparse
 import json
@@ -56,7 +60,33 @@ def parse():
     ap.add_argument("--via-optimizer", action="store_true",
                     help="drive the step through the user-facing Optimizer(...).optimize() loop (host batches fed "
                          "through its pinned double-buffered H2D feed, iteration captured in HIP graphs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned and left behind as "
+                         "DIR/<name>.npy (float32): loss.npy, the step's loss, and weights.npy, a fixed seeded sample "
+                         "of the updated fp32 master weights. Same arguments -> same inputs and the same number of "
+                         "training steps, so two builds can be compared array for array")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks that the headline figure does not need. A plain run "
+                         "sets up, warms up, times the steps and prints the result line; anything more belongs behind "
+                         "this flag (nothing does at present: both modes run the same steps)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 22      # weights.npy: this many elements (16 MB of float32) of the flat master-weight buffer
+
+
+def dump_outputs(path, loss, weights):
+    """Write the last timed step's results as float32 .npy files under ``path`` (rank 0's view; every rank holds
+    the same weights after the step's all-gather). The weight sample is drawn once from a fixed seed, sorted."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
+    w = weights.detach().float().reshape(-1).cpu()
+    if w.numel() > DUMP_SAMPLE:
+        idx = torch.randperm(w.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+        w = w[idx]
+    np.save(os.path.join(path, "weights.npy"), w.numpy())
 
 
 def _via_optimizer(args, model, crit, optim, dev, world, rank):
@@ -152,6 +182,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         ms = dt / args.steps * 1e3
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, torch.tensor(float(opt.state.get("Loss", float("nan")))),
+                         opt._step.w[:opt._step.total])
         if rank == 0:
             print(json.dumps({
                 "metric": METRIC, "value": round(B * world * args.steps / dt, 2), "unit": "images/sec",
@@ -238,6 +271,9 @@ def main():
                 run = lambda: step.step(x, y)  # noqa: E731
                 for _ in range(3):            # re-warm the caching allocator before the timed loop: a fresh device
                     run()                     # allocation can wait on the driver (seconds, measured) mid-loop
+            else:
+                for _ in range(3):            # the same three steps when the graph is kept: the number of training
+                    run()                     # steps behind --dump-outputs does not depend on the decision
     torch.cuda.synchronize()
 
     import gc
@@ -300,6 +336,8 @@ def main():
     dt = float(t.item())
     loss = float(step.loss.item()) if step.loss is not None else float("nan")
     step.flush()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.loss, step.w[:step.total])
     # device-timed phases (optim/phase_timer.py) of the eager steps (a HIP-graph replay records none: then they come
     # from the eager warm-up steps); the exposed collective wait is the max over ranks
     phase = step.phase.summary(last=args.steps) if step.phase is not None else None
