@@ -14,6 +14,12 @@ straight from the GEMM, the bias gradient as one extra ones-column of the input)
 15-40 % faster than the in-tree tiles (tools/lm_gemm_vs_blas.py, profiles/r6_lm_gemm_vs_hipblaslt.log), while the
 convolution-shaped and fused GEMMs stay on the in-tree kernels, which beat it there (tools/gemm_vs_blas.py).
 BIGDL_LINEAR_BLAS=0 keeps every Linear on the in-tree kernels.
+
+With the GEMM backend set to ``native`` (ops/gemm.py: BIGDL_GEMM_BACKEND, Engine property bigdl.gemm.backend) the
+same shapes stay in the tree on the dense bf16 GEMM of csrc/gemm_bf16.hip instead: forward = NT with the bias in the
+epilogue, data gradient = NN against the weight as stored, weight gradient = TN accumulated straight into gradWeight
+with the bias gradient as its fused column sum. That kernel is deterministic, so the route also holds in
+deterministic mode.
 """
 import math
 import os
@@ -103,6 +109,22 @@ class Linear(TensorModule):
 
         return not native.deterministic()
 
+    def _use_native(self, M):
+        """The hipBLASLt route's shapes on the in-tree dense GEMM (backend ``native``), deterministic mode included."""
+        if ops.gemm.backend() != "native":
+            return False
+        return (_BLAS[0] and not self._padded() and not self.fuse_relu
+                and _blas_shape(M, self.inputSize, self.outputSize))
+
+    def _native_fwd(self, x):
+        x16 = x if x.dtype == BF16 else (ops.to_bf16(x.contiguous()) if x.dtype == torch.float32 else x.to(BF16))
+        self._xn = x16.contiguous()
+        self._x4 = None
+        bias = self.bias
+        if bias is not None and bias.data_ptr() % 16:      # a view into the flat parameter buffer at an odd offset
+            bias = self.w16("bias")
+        return ops.gemm.gemm(self._xn, self.w16("weight"), trans_b=True, out_dtype=BF16, bias=bias)
+
     def _blas_fwd(self, x):
         """hipBLASLt forward; keeps [x | 1 | 0...] (bf16, one extra 8-column block) for the weight gradient, whose
         GEMM then yields the bias gradient as its last column."""
@@ -128,8 +150,10 @@ class Linear(TensorModule):
         elif x.dim() > 2:
             lead = x.shape[:-1]
             x = x.reshape(-1, x.shape[-1])
-        self._xe = None
-        if x.is_cuda and self._use_blas(x.shape[0]):
+        self._xe = self._xn = None
+        if x.is_cuda and self._use_native(x.shape[0]):
+            y = self._native_fwd(x)
+        elif x.is_cuda and self._use_blas(x.shape[0]):
             y = self._blas_fwd(x)
         elif x.is_cuda:
             x4 = self._x4d(x)
@@ -165,7 +189,11 @@ class Linear(TensorModule):
 
     def updateGradInput(self, input, gradOutput):
         g = self._gy2d(gradOutput)
-        if g.is_cuda and getattr(self, "_xe", None) is not None:
+        if g.is_cuda and getattr(self, "_xn", None) is not None:
+            g16 = ops.to_bf16(g) if g.dtype == torch.float32 else g.to(BF16).contiguous()
+            self._g16 = g16
+            gi = ops.gemm.gemm(g16, self.w16("weight"), out_dtype=BF16)
+        elif g.is_cuda and getattr(self, "_xe", None) is not None:
             g16 = ops.to_bf16(g) if g.dtype == torch.float32 else g.to(BF16).contiguous()
             self._g16 = g16
             gi = torch.mm(g16, self.w16("weight"))
@@ -187,6 +215,19 @@ class Linear(TensorModule):
 
     def accGradParameters(self, input, gradOutput):
         g = self._gy2d(gradOutput)
+        if g.is_cuda and getattr(self, "_xn", None) is not None:
+            g16 = getattr(self, "_g16", None)
+            if g16 is None or g16.dim() != 2 or g16.shape[0] != g.shape[0]:
+                g16 = ops.to_bf16(g) if g.dtype == torch.float32 else g.to(BF16).contiguous()
+            gb = self.gradBias if self.bias is not None else None
+            if self.gradWeight.is_contiguous() and self.gradWeight.data_ptr() % 16 == 0:
+                ops.gemm.gemm(g16, self._xn, trans_a=True, out=self.gradWeight, alpha=self.scaleW, beta=1.0,
+                              colsum=gb, colscale=self.scaleB)
+            else:       # a view into the flat gradient at an offset the 16-byte stores cannot take
+                gw = ops.gemm.gemm(g16, self._xn, trans_a=True, colsum=gb, colscale=self.scaleB)
+                self.gradWeight.add_(gw, alpha=self.scaleW)
+            self._g16 = None
+            return
         if g.is_cuda and getattr(self, "_xe", None) is not None:
             g16 = getattr(self, "_g16", None)
             if g16 is None or g16.dim() != 2 or g16.shape[0] != g.shape[0]:

@@ -295,6 +295,15 @@ def _recurrent_wgrad_blas(rows, H, n=None):
     return _RWG_BLAS[0] and linear._blas_shape(rows, H, n) and not ops.native.deterministic()
 
 
+def _recurrent_wgrad_native(rows, H, n=None):
+    """The same GEMMs on the in-tree dense bf16 kernel (ops/gemm.py, backend ``native``); deterministic, so the
+    route also holds in deterministic mode."""
+    from . import linear
+
+    n = 4 * H if n is None else n
+    return ops.gemm.backend() == "native" and _RWG_BLAS[0] and linear._blas_shape(rows, H, n)
+
+
 class _LSTMSeq(torch.autograd.Function):
     """Whole-sequence LSTM (gate order i, g, f, o) with the fused HIP cell kernels on the GPU engine."""
 
@@ -408,6 +417,13 @@ class _LSTMSeq(torch.autograd.Function):
                            dcT.contiguous() if dcT is not None else None, acts, cs, c0.contiguous(), dg16, dxg, dc0,
                            dh0, sync)
             sink = _live_sink(ctx.gmod)
+            if _recurrent_wgrad_native(T * B, H):
+                # dU (+)= dg^T h as one TN GEMM, accumulated in place (beta = 1) into the fp32 gradient
+                a, b = dg16.view(T * B, 4 * H), h16[:T].view(T * B, H)
+                if sink is not None and sink.is_contiguous() and sink.data_ptr() % 16 == 0:
+                    ops.gemm.gemm(a, b, trans_a=True, out=sink, beta=1.0)
+                    return dxg, dh0, dc0, None, None
+                return dxg, dh0, dc0, ops.gemm.gemm(a, b, trans_a=True), None
             if _recurrent_wgrad_blas(T * B, H):
                 # dU (+)= dg^T h over all T * B rows on hipBLASLt, accumulated in place (beta = 1) into the fp32
                 # gradient: the [4H x H x T*B] GEMM is the shape the Linear route measured fastest there
@@ -535,6 +551,8 @@ class _GRUSeq(torch.autograd.Function):
             C.gru_seq_bwd(Wrz, Wn, h0, gates, out, dout.contiguous() if dout is not None else None,
                           dhT.contiguous() if dhT is not None else None, dx, dn16, drz16, dh0, sync)
             def wgrad(g16, x16, n):        # [n, H] = g^T x over all T * B rows (hipBLASLt where the LSTM's rule says)
+                if _recurrent_wgrad_native(T * B, H, n):
+                    return ops.gemm.gemm(g16.view(T * B, n), x16.view(T * B, H), trans_a=True)
                 if _recurrent_wgrad_blas(T * B, H, n):
                     return torch.mm(g16.view(T * B, n).t(), x16.view(T * B, H), out_dtype=torch.float32)
                 d = out.new_empty(n, H, 1, 1)

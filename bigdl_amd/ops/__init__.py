@@ -8,6 +8,7 @@ import torch
 
 from . import native  # noqa: F401
 from . import conv, bn, pool  # noqa: F401
+from . import gemm  # noqa: F401
 
 BF16 = torch.bfloat16
 CL = torch.channels_last

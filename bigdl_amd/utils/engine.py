@@ -163,6 +163,10 @@ class _Engine:
             from ..ops import native
 
             native.set_deterministic(str(v).lower() in ("1", "true", "yes"))
+        elif k == "bigdl.gemm.backend":             # "blas" | "native": who runs the LM-scale plain GEMMs (ops/gemm.py)
+            from ..ops import gemm
+
+            gemm.set_backend(v)
         elif k == "bigdl.module.deviceTiming":      # getTimes in device time (HIP events) for GPU modules
             from ..nn import abstractnn
 

@@ -331,6 +331,68 @@ void bmm_nt(const Tensor& a, const Tensor& b, const Tensor& c, double alpha, boo
                               b.stride(1), c.stride(1), (float)alpha, accum ? 1 : 0, stream());
   TORCH_CHECK(rc == 0, "bmm_nt: unsupported shape");
 }
+// ---- dense bf16 GEMM (gemm_bf16.hip). form 0 NT: a [M,K], b [N,K]; 1 NN: a [M,K], b [K,N]; 2 TN: a [P,M], b [P,N].
+// Row-strided views are accepted (stride(1) == 1, stride(0) a multiple of 8 elements).
+static void gemm_operand(const Tensor& t, const char* n, bool bf16_only) {
+  TORCH_CHECK(t.is_cuda(), "gemm_bf16: ", n, " must be a GPU tensor");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 || (!bf16_only && t.scalar_type() == at::kFloat), "gemm_bf16: ", n,
+              " has dtype ", t.scalar_type());
+  TORCH_CHECK(t.dim() == 2 && t.size(0) > 0 && t.size(1) > 0, "gemm_bf16: ", n, " must be a non-empty matrix");
+  TORCH_CHECK(t.stride(1) == 1, "gemm_bf16: the inner dimension of ", n, " must be contiguous");
+  TORCH_CHECK(t.size(1) % 8 == 0, "gemm_bf16: the inner extent of ", n, " must be a multiple of 8 elements");
+  TORCH_CHECK(t.size(0) == 1 || (t.stride(0) % 8 == 0 && t.stride(0) >= t.size(1)), "gemm_bf16: the leading dimension of ",
+              n, " must be a multiple of 8 elements and cover a row");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "gemm_bf16: ", n, " must be 16-byte aligned");
+}
+int64_t gemm_bf16_ws_bytes(int64_t form, int64_t M, int64_t N, int64_t K) {
+  return (int64_t)bigdl_gemm_bf16_ws_bytes((int)form, (int)M, (int)N, (int)K);
+}
+void gemm_bf16(const Tensor& a, const Tensor& b, const Tensor& out, int64_t form, double alpha, double beta,
+               const OptT& bias, const OptT& colsum, double colscale, const OptT& ws) {
+  TORCH_CHECK(form >= 0 && form <= 2, "gemm_bf16: form is 0 (NT), 1 (NN) or 2 (TN)");
+  gemm_operand(a, "a", true); gemm_operand(b, "b", true); gemm_operand(out, "out", false);
+  const int64_t M = form == 2 ? a.size(1) : a.size(0), K = form == 2 ? a.size(0) : a.size(1);
+  const int64_t N = form == 0 ? b.size(0) : b.size(1), Kb = form == 0 ? b.size(1) : b.size(0);
+  TORCH_CHECK(K == Kb, "gemm_bf16: reduction lengths differ (", K, " vs ", Kb, ")");
+  TORCH_CHECK(out.size(0) == M && out.size(1) == N, "gemm_bf16: out must be [", M, ", ", N, "]");
+  TORCH_CHECK(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "gemm_bf16: extent too large");
+  const bool obf = out.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(!(obf && beta != 0.0), "gemm_bf16: beta needs an fp32 out");
+  GemmBf16Args g = {};
+  g.a = reinterpret_cast<const uint16_t*>(a.data_ptr());
+  g.b = reinterpret_cast<const uint16_t*>(b.data_ptr());
+  g.c = out.data_ptr();
+  auto ld = [](const Tensor& t) { return t.size(0) == 1 ? t.size(1) : t.stride(0); };
+  TORCH_CHECK(ld(a) < (1ll << 31) && ld(b) < (1ll << 31) && ld(out) < (1ll << 31), "gemm_bf16: leading dimension too large");
+  g.form = (int)form; g.M = (int)M; g.N = (int)N; g.K = (int)K;
+  g.lda = (int)ld(a); g.ldb = (int)ld(b); g.ldc = (int)ld(out);
+  g.out_bf16 = obf ? 1 : 0;
+  g.alpha = (float)alpha; g.beta = (float)beta; g.colscale = (float)colscale;
+  if (bias && bias->defined()) {
+    TORCH_CHECK(form != 2, "gemm_bf16: bias is for the NT / NN forms");
+    TORCH_CHECK(bias->is_cuda() && bias->dim() == 1 && bias->size(0) == N && bias->is_contiguous() &&
+                (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16), "gemm_bf16: bias must be a dense fp32 / bf16 GPU vector of N");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(bias->data_ptr()) % 16 == 0, "gemm_bf16: bias must be 16-byte aligned");
+    g.bias = bias->data_ptr();
+    g.bias_bf16 = bias->scalar_type() == at::kBFloat16 ? 1 : 0;
+  }
+  if (colsum && colsum->defined()) {
+    TORCH_CHECK(form == 2, "gemm_bf16: colsum is for the TN form");
+    TORCH_CHECK(colsum->dim() == 1 && colsum->size(0) == M && colsum->is_contiguous(), "gemm_bf16: colsum must be a dense vector of M");
+    g.colsum = mf(*colsum, "colsum");
+  }
+  const size_t need = bigdl_gemm_bf16_ws_bytes(g.form, g.M, g.N, g.K);
+  size_t have = 0;
+  if (need > 0) {
+    TORCH_CHECK(ws && ws->defined() && ws->is_cuda() && ws->is_contiguous(), "gemm_bf16: this shape splits its reduction and needs a workspace");
+    have = (size_t)ws->numel() * ws->element_size();
+    TORCH_CHECK(have >= need && reinterpret_cast<uintptr_t>(ws->data_ptr()) % 16 == 0, "gemm_bf16: workspace too small or misaligned (need ", need, " bytes)");
+    g.ws = reinterpret_cast<float*>(ws->data_ptr());
+  }
+  const int rc = bigdl_gemm_bf16(&g, have, stream());
+  TORCH_CHECK(rc != -2, "gemm_bf16: an operand's byte extent does not fit a 32-bit buffer offset");
+  TORCH_CHECK(rc == 0, "gemm_bf16: unsupported arguments (", rc, ")");
+}
 // ---- TensorMath backend (tensor_math.hip): operands are fp32 GPU tensors already broadcast to the output's
 // sizes; the Python side collapses dimensions and passes per-operand strides (elements)
 void tensor_apply(const Tensor& out, const OptT& a, const OptT& b, const OptT& c, std::vector<int64_t> size,
@@ -1430,6 +1492,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk_f32", &topk_f32);
   m.def("gemv_f32", &gemv_f32);
   m.def("fill_bytes", &fill_bytes);
+  m.def("gemm_bf16", &gemm_bf16, py::arg("a"), py::arg("b"), py::arg("out"), py::arg("form"), py::arg("alpha") = 1.0,
+        py::arg("beta") = 0.0, py::arg("bias") = py::none(), py::arg("colsum") = py::none(), py::arg("colscale") = 1.0,
+        py::arg("ws") = py::none());
+  m.def("gemm_bf16_ws_bytes", &gemm_bf16_ws_bytes);
   m.def("copy_rows_i8", &copy_rows_i8);
   m.def("cast_f32_bf16", &cast_f32_bf16);
   m.def("cast_bf16_f32", &cast_bf16_f32);

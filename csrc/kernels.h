@@ -419,4 +419,27 @@ typedef struct {
   int N, C, H, W, K, OH, OW, R, S, sh, sw, ph, pw, dh, dw, G;
 } GConvCall;
 int bigdl_gconv(const GConvCall* c, int pass, hipStream_t st);
+
+// Dense bf16 GEMM (gemm_bf16.hip): C = alpha * op(A) * op(B) + bias[n] + beta * C over row-major bf16 operands.
+// form 0 NT: A[M,K], B[N,K]; 1 NN: A[M,K], B[K,N]; 2 TN: A[K,M], B[K,N] (K = the reduction length in every form).
+// Inner extents and leading dimensions (elements) are multiples of 8, bases 16-byte aligned. c is fp32 (beta
+// allowed) or bf16; bias (NT / NN) fp32 or bf16 of N; colsum (TN) fp32 of M: colsum[m] += colscale * sum_k A[k][m].
+// ws: bigdl_gemm_bf16_ws_bytes(form, M, N, K) bytes (0 when the reduction is not split). The *_bytes / kt_per
+// fields are filled by the host entry.
+typedef struct {
+  const uint16_t* a;
+  const uint16_t* b;
+  void* c;
+  const void* bias;
+  float* colsum;
+  float* ws;
+  int form, M, N, K;
+  int lda, ldb, ldc;
+  int out_bf16, bias_bf16;
+  float alpha, beta, colscale;
+  unsigned a_bytes, b_bytes, c_bytes;
+  int kt_per;
+} GemmBf16Args;
+size_t bigdl_gemm_bf16_ws_bytes(int form, int M, int N, int K);
+int bigdl_gemm_bf16(const GemmBf16Args* a, size_t ws_bytes, hipStream_t st);
 }
