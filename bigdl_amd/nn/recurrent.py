@@ -17,7 +17,9 @@ of the cell weights, so backward is a single reverse sweep. LSTM (tanh/sigmoid, 
 loop entirely: a sequence-level autograd Function runs ``h @ U^T`` (library GEMM) + the fused HIP cell kernel
 (csrc/elementwise.hip lstm_fwd_kernel / lstm_bwd_kernel: all four gate nonlinearities, the cell update and
 the gradient of both in one pass) per step, and computes dU with ONE [4H, T*B] x [T*B, H] GEMM after the
-reverse sweep instead of T small ones.
+reverse sweep instead of T small ones. LSTMPeephole (p == 0) and the maskZero LSTM take the same shape of path on
+the GPU (``_LSTMPeepSeq``: csrc/lstm_peephole.hip, one fused launch per step with peephole terms and a row mask in
+the cell epilogue); every other masked cell runs the generic loop.
 """
 import os
 
@@ -483,6 +485,176 @@ class _LSTMSeq(torch.autograd.Function):
         return dgs.transpose(0, 1), dh_next, dc_next, dU, None
 
 
+# BIGDL_LSTM_PEEP_FUSED=0 sends LSTMPeephole and the maskZero LSTM back to the Python time loop (Cell.sequence) (A/B)
+_PEEP_FUSED = [os.environ.get("BIGDL_LSTM_PEEP_FUSED", "1") != "0"]
+
+
+class _LSTMPeepSeq(torch.autograd.Function):
+    """Whole-sequence LSTM with optional peepholes (pI, pF on c_{t-1}, pO on c_t), an optional [B, T] row mask
+    (True = valid; a masked row keeps h and c, emits 0 and hands its recurrent gradient on unchanged: Cell.sequence's
+    maskZero semantics) and a gate layout: ``order`` = positions of the i, f, g, o blocks in the [4H] gate axis of xg
+    and U ((0, 2, 1, 3) for nn.LSTM, (0, 1, 2, 3) for nn.LSTMPeephole).
+
+    GPU (fp32 xg, H % 32 == 0): one fused launch per step and direction (csrc/lstm_peephole.hip), the recurrent weight
+    gradient as one native GEMM after the sweep, the peephole gradients by a fixed-order reduction kernel. Other
+    tensors: the same forward and the same hand-derived backward in plain torch, in the tensors' own dtype (the
+    modules do not route the CPU engine here; it keeps the formulas checkable in fp64)."""
+
+    ORDER_LSTM = (0, 2, 1, 3)
+    ORDER_PEEPHOLE = (0, 1, 2, 3)
+
+    @staticmethod
+    def usable(x2, H):
+        return (_PEEP_FUSED[0] and x2.is_cuda and x2.dim() == 3 and x2.dtype == torch.float32 and H % 32 == 0
+                and x2.shape[1] > 0)
+
+    @staticmethod
+    def forward(ctx, xg, h0, c0, U, pI, pF, pO, mask, order):
+        ctx.set_materialize_grads(False)
+        B, T, G = xg.shape
+        H = G // 4
+        order = tuple(int(k) for k in order)
+        assert sorted(order) == [0, 1, 2, 3], "order: positions of the i, f, g, o gate blocks"
+        peep = pI is not None
+        assert (pF is not None) == peep and (pO is not None) == peep, "peepholes: all three or none"
+        ctx.order, ctx.peep = order, peep
+        ctx.pshapes = [p.shape for p in (pI, pF, pO)] if peep else None
+        if mask is not None:
+            mask = mask.bool()
+        ctx.fused = xg.is_cuda and xg.dtype == torch.float32 and H % 32 == 0
+        if ctx.fused:
+            C = ops.native.get()
+            xg = xg.contiguous()
+            W16 = ops.to_bf16(U.detach())
+            ps = [p.detach().reshape(H).contiguous() for p in (pI, pF, pO)] if peep else [None, None, None]
+            # time-major bytes: step t's mask is one contiguous [B] row
+            mt = mask.t().contiguous().view(torch.uint8) if mask is not None else None
+            out = xg.new_empty(B, T, H)
+            cs = xg.new_empty(T, B, H)
+            acts = xg.new_empty(T, B, G)
+            h16 = xg.new_empty(T + 1, B, H, dtype=torch.bfloat16)
+            C.cast_f32_bf16(h0.contiguous(), h16[0])
+            # fp32 h state, written in place by valid rows only: a masked row's h is carried exactly
+            hst = h0.contiguous().clone() if mt is not None else None
+            c_prev = c0.contiguous()
+            for t in range(T):
+                C.lstm_peep_fwd_step(W16, h16[t], xg[:, t], c_prev, cs[t], hst, out[:, t], h16[t + 1], acts[t],
+                                     ps[0], ps[1], ps[2], mt[t] if mt is not None else None, order)
+                c_prev = cs[t]
+            ctx.save_for_backward(c0, U, cs, acts, h16, W16, mt, *ps)
+            return out, (hst if hst is not None else out[:, -1].clone()), cs[-1].clone()
+        pi, pf, pg, po = order
+        Ut = U.t()
+        h, c = h0, c0
+        hs, cs, gi, gf, gg, go = ([] for _ in range(6))
+        for t in range(T):
+            g = xg[:, t] + h @ Ut
+            ai, af = g[:, pi * H:(pi + 1) * H], g[:, pf * H:(pf + 1) * H]
+            if peep:
+                ai, af = ai + pI * c, af + pF * c
+            i, f, gc = torch.sigmoid(ai), torch.sigmoid(af), torch.tanh(g[:, pg * H:(pg + 1) * H])
+            c2 = f * c + i * gc
+            ao = g[:, po * H:(po + 1) * H]
+            if peep:
+                ao = ao + pO * c2
+            o = torch.sigmoid(ao)
+            h2 = o * torch.tanh(c2)
+            if mask is not None:
+                m = mask[:, t].unsqueeze(1)
+                h2, c2 = torch.where(m, h2, h), torch.where(m, c2, c)
+            h, c = h2, c2
+            hs.append(h); cs.append(c); gi.append(i); gf.append(f); gg.append(gc); go.append(o)
+        hs, cs = torch.stack(hs), torch.stack(cs)
+        out = hs.transpose(0, 1)
+        if mask is not None:
+            out = out * mask.unsqueeze(2).to(out.dtype)
+        ctx.save_for_backward(h0, c0, U, hs, cs, torch.stack(gi), torch.stack(gf), torch.stack(gg), torch.stack(go),
+                              mask, pI, pF, pO)
+        return out.contiguous(), hs[-1].clone(), cs[-1].clone()
+
+    @staticmethod
+    def _backward_fused(ctx, dout, dhT, dcT):
+        from ..ops import conv as cv
+
+        c0, U, cs, acts, h16, W16, mt, pI, pF, pO = ctx.saved_tensors
+        T, B, H = cs.shape
+        C = ops.native.get()
+        order = ctx.order
+        dout = dout.contiguous() if dout is not None else None
+        WT16 = cv.transpose_w(W16.view(4 * H, H, 1, 1)).view(H, 4 * H)
+        dxg = cs.new_empty(B, T, 4 * H)
+        dg16 = cs.new_empty(T, B, 4 * H, dtype=torch.bfloat16)      # time-major: rows t*B + b
+        dc = dcT.contiguous().clone() if dcT is not None else ops.zeros(B, H, device=cs.device)
+        dhT = dhT.contiguous() if dhT is not None else None
+        carry = None
+        if mt is not None:
+            # the gradient of the final h is what a masked last step hands on: it starts the carry
+            carry = dhT.clone() if dhT is not None else ops.zeros(B, H, device=cs.device)
+            dhT = None
+        c0 = c0.contiguous()
+        for t in range(T - 1, -1, -1):
+            C.lstm_peep_bwd_step(WT16, dg16[t + 1] if t < T - 1 else None,
+                                 dout[:, t] if dout is not None else None, dhT if t == T - 1 else None, acts[t],
+                                 cs[t - 1] if t > 0 else c0, cs[t], dc, carry, dxg[:, t], dg16[t], pI, pF, pO,
+                                 mt[t] if mt is not None else None, order)
+        dh0, dU = _rnn_param_grads(dg16, h16, U, WT16)
+        if carry is not None:
+            dh0 = dh0 + carry
+        dps = [None, None, None]
+        if ctx.peep:
+            part = cs.new_empty(C.lstm_peep_wgrad_slices(T * B), 3, H)
+            dp = cs.new_empty(3, H)
+            C.lstm_peep_wgrad(dxg, cs, c0, part, dp, order)
+            dps = [dp[k].reshape(s) for k, s in enumerate(ctx.pshapes)]
+        return (dxg, dh0, dc, dU, *dps, None, None)
+
+    @staticmethod
+    def backward(ctx, dout, dhT, dcT):
+        if ctx.fused:
+            return _LSTMPeepSeq._backward_fused(ctx, dout, dhT, dcT)
+        h0, c0, U, hs, cs, gi, gf, gg, go, mask, pI, pF, pO = ctx.saved_tensors
+        T, B, H = hs.shape
+        pi, pf, pg, po = ctx.order
+        peep = ctx.peep
+        dh_rec = dhT if dhT is not None else torch.zeros_like(h0)     # the recurrent gradient arriving for h_t
+        dc = dcT if dcT is not None else torch.zeros_like(c0)
+        dgs = hs.new_zeros(T, B, 4 * H)
+        dps = [torch.zeros_like(pI), torch.zeros_like(pF), torch.zeros_like(pO)] if peep else [None, None, None]
+        for t in range(T - 1, -1, -1):
+            c_prev = cs[t - 1] if t > 0 else c0
+            i, f, gc, o, c = gi[t], gf[t], gg[t], go[t], cs[t]
+            dh = dh_rec + dout[:, t] if dout is not None else dh_rec
+            tc = torch.tanh(c)
+            do_ = dh * tc * o * (1 - o)
+            dcv = dh * o * (1 - tc * tc) + dc
+            if peep:
+                dcv = dcv + do_ * pO
+            di_ = dcv * gc * i * (1 - i)
+            df_ = dcv * c_prev * f * (1 - f)
+            dg_ = dcv * i * (1 - gc * gc)
+            dc_prev = dcv * f
+            if peep:
+                dc_prev = dc_prev + di_ * pI + df_ * pF
+            dgt = dgs[t]
+            for k, v in ((pi, di_), (pf, df_), (pg, dg_), (po, do_)):
+                dgt[:, k * H:(k + 1) * H] = v
+            if mask is not None:
+                m = mask[:, t].unsqueeze(1)
+                dgt.mul_(m.to(dgt.dtype))                  # masked row: no gate gradient, dc passes through,
+                dc = torch.where(m, dc_prev, dc)           # and the recurrent gradient is handed on unchanged
+                dh_rec = dgt @ U + torch.where(m, torch.zeros_like(dh_rec), dh_rec)
+            else:
+                dc = dc_prev
+                dh_rec = dgt @ U
+            if peep:
+                dps[0] = dps[0] + (dgt[:, pi * H:(pi + 1) * H] * c_prev).sum(0).reshape(pI.shape)
+                dps[1] = dps[1] + (dgt[:, pf * H:(pf + 1) * H] * c_prev).sum(0).reshape(pF.shape)
+                dps[2] = dps[2] + (dgt[:, po * H:(po + 1) * H] * c).sum(0).reshape(pO.shape)
+        hprev = torch.cat([h0.unsqueeze(0), hs[:-1]], 0).reshape(T * B, H)
+        dU = dgs.reshape(T * B, 4 * H).t() @ hprev
+        return (dgs.transpose(0, 1), dh_rec, dc, dU, *dps, None, None)
+
+
 class _GRUSeq(torch.autograd.Function):
     """Whole-sequence GRU (preTopology order r, z, n). Where the persistent kernels apply (B <= 128 per GPU,
     H in {256, 512, 1024}: csrc/lstm_seq.hip gru_seq_*_kernel) the whole sequence is ONE launch per direction (the
@@ -759,6 +931,11 @@ class LSTM(Cell):
         if mask is None and self._fused_ok():
             out, h, c = _LSTMSeq.apply(x2.contiguous(), hid[0], hid[1], self.h2g.weight, self._grad_sink(self.h2g))
             return out, [h, c]
+        if mask is not None and self._fused_ok() and _LSTMPeepSeq.usable(x2, self.hiddenSize):
+            # maskZero on the GPU: the masked step kernels (csrc/lstm_peephole.hip), no peepholes
+            out, h, c = _LSTMPeepSeq.apply(x2, hid[0], hid[1], self.h2g.weight, None, None, None, mask,
+                                           _LSTMPeepSeq.ORDER_LSTM)
+            return out, [h, c]
         default_act = _is(self.activation, Tanh) and _is(self.innerActivation, Sigmoid)
         if self.p != 0 and mask is None and default_act:
             if self.train and _LSTMDropSeq.usable(x2, self.hiddenSize, self.inputSize):
@@ -799,6 +976,14 @@ class LSTMPeephole(Cell):
         o = torch.sigmoid(g[:, 3 * H:] + self.peepO.weight * c2)
         h2 = o * torch.tanh(c2)
         return h2, [h2, c2]
+
+    def sequence(self, x2, hid, mask=None):
+        if self.p == 0 and _LSTMPeepSeq.usable(x2, self.hiddenSize):
+            # GPU: one fused step kernel per time step and direction (csrc/lstm_peephole.hip), with or without a mask
+            out, h, c = _LSTMPeepSeq.apply(x2, hid[0], hid[1], self.h2g.weight, self.peepI.weight, self.peepF.weight,
+                                           self.peepO.weight, mask, _LSTMPeepSeq.ORDER_PEEPHOLE)
+            return out, [h, c]
+        return super().sequence(x2, hid, mask)
 
 
 class GRU(Cell):

@@ -1176,6 +1176,109 @@ void lstm_bwd_step(const Tensor& WT16, const OptT& dg16_next, const OptT& dout, 
                       ldg, mbf(dg16_out, "dg16_out"), B, H, stream());
 }
 
+// Fused LSTM steps with optional peepholes / row mask and a gate layout (csrc/lstm_peephole.hip). order = positions of
+// the i, f, g, o blocks in the [4H] gate axis; pI / pF / pO fp32 [H], all or none; mask = this step's [B] uint8 or bool.
+struct PeepArgs {
+  const float *pI = nullptr, *pF = nullptr, *pO = nullptr;
+  const unsigned char* mask = nullptr;
+  int g[4] = {0, 1, 2, 3};
+};
+PeepArgs peep_args(const char* fn, const OptT& pI, const OptT& pF, const OptT& pO, const OptT& mask,
+                   const std::vector<int64_t>& order, int64_t B, int64_t H) {
+  PeepArgs a;
+  const bool hi = pI && pI->defined(), hf = pF && pF->defined(), ho = pO && pO->defined();
+  TORCH_CHECK(hi == hf && hi == ho, fn, ": peepholes pI, pF, pO must be given all three or not at all");
+  if (hi) {
+    for (const Tensor* p : {&*pI, &*pF, &*pO})
+      TORCH_CHECK(p->numel() == H && p->is_contiguous(), fn, ": peepholes must be [H] contiguous");
+    a.pI = cf(*pI, "pI"); a.pF = cf(*pF, "pF"); a.pO = cf(*pO, "pO");
+  }
+  if (mask && mask->defined()) {
+    TORCH_CHECK(mask->is_cuda() && (mask->scalar_type() == at::kByte || mask->scalar_type() == at::kBool), fn,
+                ": mask must be a uint8 or bool GPU tensor");
+    TORCH_CHECK(mask->numel() == B && mask->is_contiguous(), fn, ": mask must be [B] contiguous");
+    a.mask = (const unsigned char*)mask->data_ptr();
+  }
+  TORCH_CHECK(order.size() == 4, fn, ": order must hold the positions of the i, f, g, o gate blocks");
+  int seen = 0;
+  for (int k = 0; k < 4; ++k) {
+    TORCH_CHECK(order[k] >= 0 && order[k] < 4, fn, ": gate positions must be in 0..3");
+    seen |= 1 << order[k];
+    a.g[k] = (int)order[k];
+  }
+  TORCH_CHECK(seen == 15, fn, ": gate positions must be a permutation of 0..3");
+  return a;
+}
+void lstm_peep_fwd_step(const Tensor& W16, const OptT& h16_prev, const Tensor& xg, const OptT& c_prev,
+                        const Tensor& c_out, const OptT& h_state, const Tensor& h_out, const Tensor& h16_out,
+                        const Tensor& acts, const OptT& pI, const OptT& pF, const OptT& pO, const OptT& mask,
+                        const std::vector<int64_t>& order) {
+  const int64_t B = xg.size(0), H = W16.size(1);
+  TORCH_CHECK(W16.dim() == 2 && W16.size(0) == 4 * H && W16.is_contiguous(),
+              "lstm_peep_fwd_step: W16 must be [4H, H] contiguous");
+  TORCH_CHECK(H > 0 && H % 32 == 0 && B >= 1, "lstm_peep_fwd_step: H must be a multiple of 32, B >= 1");
+  const int64_t ldx = rowstride(xg, 4 * H, "xg"), ldh = rowstride(h_out, H, "h_out"), lda = rowstride(acts, 4 * H, "acts");
+  TORCH_CHECK(h_out.size(0) == B && acts.size(0) == B && c_out.numel() == B * H && h16_out.numel() == B * H,
+              "lstm_peep_fwd_step: batch mismatch");
+  TORCH_CHECK(c_out.is_contiguous() && h16_out.is_contiguous(), "lstm_peep_fwd_step: c_out/h16_out contiguous");
+  if (h16_prev && h16_prev->defined()) TORCH_CHECK(h16_prev->numel() == B * H && h16_prev->is_contiguous(), "h16_prev");
+  if (c_prev && c_prev->defined()) TORCH_CHECK(c_prev->numel() == B * H && c_prev->is_contiguous(), "c_prev");
+  if (h_state && h_state->defined()) TORCH_CHECK(h_state->numel() == B * H && h_state->is_contiguous(), "h_state");
+  const PeepArgs a = peep_args("lstm_peep_fwd_step", pI, pF, pO, mask, order, B, H);
+  const int rc = bigdl_lstm_peep_fwd_step(cbf(W16, "W16"), ocbf(h16_prev, "h16_prev"), cf(xg, "xg"), ldx,
+                                          ocf(c_prev, "c_prev"), mf(c_out, "c_out"), omf(h_state, "h_state"),
+                                          mf(h_out, "h_out"), ldh, mbf(h16_out, "h16_out"), mf(acts, "acts"), lda,
+                                          a.pI, a.pF, a.pO, a.mask, a.g[0], a.g[1], a.g[2], a.g[3], (int)B, (int)H,
+                                          stream());
+  TORCH_CHECK(rc == 0, "lstm_peep_fwd_step: unsupported arguments");
+}
+void lstm_peep_bwd_step(const Tensor& WT16, const OptT& dg16_next, const OptT& dout, const OptT& dh_ext,
+                        const Tensor& acts, const OptT& c_prev, const Tensor& c_t, const Tensor& dc, const OptT& carry,
+                        const Tensor& dg_out, const Tensor& dg16_out, const OptT& pI, const OptT& pF, const OptT& pO,
+                        const OptT& mask, const std::vector<int64_t>& order) {
+  const int64_t H = WT16.size(0), B = acts.size(0);
+  TORCH_CHECK(WT16.dim() == 2 && WT16.size(1) == 4 * H && WT16.is_contiguous(),
+              "lstm_peep_bwd_step: WT16 must be [H, 4H] contiguous");
+  TORCH_CHECK(H > 0 && H % 32 == 0 && B >= 1, "lstm_peep_bwd_step: H must be a multiple of 32, B >= 1");
+  const int64_t lda = rowstride(acts, 4 * H, "acts"), ldg = rowstride(dg_out, 4 * H, "dg_out");
+  int64_t ldd = 0;
+  if (dout && dout->defined()) { ldd = rowstride(*dout, H, "dout"); TORCH_CHECK(dout->size(0) == B, "dout batch"); }
+  TORCH_CHECK(dg_out.size(0) == B && c_t.numel() == B * H && dc.numel() == B * H && dg16_out.numel() == B * 4 * H,
+              "lstm_peep_bwd_step: batch mismatch");
+  TORCH_CHECK(c_t.is_contiguous() && dc.is_contiguous() && dg16_out.is_contiguous(), "lstm_peep_bwd_step: contiguity");
+  if (dg16_next && dg16_next->defined()) TORCH_CHECK(dg16_next->numel() == B * 4 * H && dg16_next->is_contiguous(), "dg16_next");
+  if (dh_ext && dh_ext->defined()) TORCH_CHECK(dh_ext->numel() == B * H && dh_ext->is_contiguous(), "dh_ext");
+  if (c_prev && c_prev->defined()) TORCH_CHECK(c_prev->numel() == B * H && c_prev->is_contiguous(), "c_prev");
+  const bool has_carry = carry && carry->defined();
+  if (has_carry) TORCH_CHECK(carry->numel() == B * H && carry->is_contiguous(), "carry");
+  const PeepArgs a = peep_args("lstm_peep_bwd_step", pI, pF, pO, mask, order, B, H);
+  TORCH_CHECK(a.mask == nullptr || has_carry, "lstm_peep_bwd_step: a mask needs the carry buffer");
+  const int rc = bigdl_lstm_peep_bwd_step(cbf(WT16, "WT16"), ocbf(dg16_next, "dg16_next"), ocf(dout, "dout"), ldd,
+                                          ocf(dh_ext, "dh_ext"), cf(acts, "acts"), lda, ocf(c_prev, "c_prev"),
+                                          cf(c_t, "c_t"), mf(dc, "dc"), omf(carry, "carry"), mf(dg_out, "dg_out"), ldg,
+                                          mbf(dg16_out, "dg16_out"), a.pI, a.pF, a.pO, a.mask, a.g[0], a.g[1], a.g[2],
+                                          a.g[3], (int)B, (int)H, stream());
+  TORCH_CHECK(rc == 0, "lstm_peep_bwd_step: unsupported arguments");
+}
+// Peephole weight gradients out [3, H] = (dp_i, dp_f, dp_o) from dg [B, T, 4H] (any batch / time strides, unit inner
+// stride), cs [T, B, H], c0 [B, H]; part = fp32 workspace of lstm_peep_wgrad_slices(T * B) * 3 * H elements.
+int64_t lstm_peep_wgrad_slices(int64_t rows) { return bigdl_lstm_peep_wgrad_slices(rows); }
+void lstm_peep_wgrad(const Tensor& dg, const Tensor& cs, const OptT& c0, const Tensor& part, const Tensor& out,
+                     const std::vector<int64_t>& order) {
+  TORCH_CHECK(dg.dim() == 3 && cs.dim() == 3 && cs.is_contiguous(), "lstm_peep_wgrad: dg [B, T, 4H], cs [T, B, H] contiguous");
+  const int64_t B = dg.size(0), T = dg.size(1), H = cs.size(2);
+  TORCH_CHECK(H > 0 && H % 32 == 0 && B >= 1 && T >= 1, "lstm_peep_wgrad: H must be a multiple of 32, B, T >= 1");
+  TORCH_CHECK(dg.size(2) == 4 * H && dg.stride(2) == 1 && cs.size(0) == T && cs.size(1) == B, "lstm_peep_wgrad: shapes");
+  if (c0 && c0->defined()) TORCH_CHECK(c0->numel() == B * H && c0->is_contiguous(), "lstm_peep_wgrad: c0");
+  TORCH_CHECK(part.is_contiguous() && part.numel() >= bigdl_lstm_peep_wgrad_slices(T * B) * 3 * H, "lstm_peep_wgrad: part");
+  TORCH_CHECK(out.is_contiguous() && out.numel() == 3 * H, "lstm_peep_wgrad: out must be [3, H] contiguous");
+  const PeepArgs a = peep_args("lstm_peep_wgrad", OptT(), OptT(), OptT(), OptT(), order, B, H);
+  const int rc = bigdl_lstm_peep_wgrad(cf(dg, "dg"), dg.stride(0), dg.stride(1), cf(cs, "cs"), ocf(c0, "c0"),
+                                       mf(part, "part"), mf(out, "out"), a.g[0], a.g[1], a.g[2], a.g[3], (int)T, (int)B,
+                                       (int)H, stream());
+  TORCH_CHECK(rc == 0, "lstm_peep_wgrad: unsupported arguments");
+}
+
 // Whole-sequence persistent GRU (csrc/lstm_seq.hip): Wrz16 [2H, H], Wn16 [H, H] bf16; xg [B, T, 3H] f32 (r|z|n),
 // h16 [T + 1, B, H] bf16 (h16[0] = h0), rh16 [T, B, H] bf16, gates [3, T, B, H] f32, out [B, T, H] f32.
 bool gru_seq_supported(int64_t B, int64_t H) { return bigdl_gru_seq_supported((int)B, (int)H) != 0; }
@@ -1550,6 +1653,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("f32_to_bf16_rtz", &f32_to_bf16_rtz);
   m.def("lstm_fwd_step", &lstm_fwd_step);
   m.def("lstm_bwd_step", &lstm_bwd_step);
+  m.def("lstm_peep_fwd_step", &lstm_peep_fwd_step);
+  m.def("lstm_peep_bwd_step", &lstm_peep_bwd_step);
+  m.def("lstm_peep_wgrad_slices", &lstm_peep_wgrad_slices);
+  m.def("lstm_peep_wgrad", &lstm_peep_wgrad);
   m.def("lstm_seq_supported", &lstm_seq_supported);
   m.def("set_lstm_seq", &bigdl_set_lstm_seq);
   m.def("lstm_seq_sync_words", &lstm_seq_sync_words);

@@ -74,6 +74,31 @@ def main():
     # same-t (no strided walk over the sequence): isolates TLB / first-touch effects of the [B, T, *] layouts
     print(f"fwd step fixed t       {timeit(lambda t=0: fwd(5)):7.2f} us")
     print(f"bwd step fixed t       {timeit(lambda t=0: bwd(5)):7.2f} us")
+    if os.environ.get("PEEP", "0") != "0":
+        # csrc/lstm_peephole.hip next to the rows above: once with neither peepholes nor mask (the margin the general
+        # epilogue loses to the specialised kernel), once with both (every fourth row masked)
+        peeps = [torch.randn(H, device=dev) * 0.1 for _ in range(3)]
+        mask = (torch.arange(B, device=dev) % 4 != 3).to(torch.uint8)
+        hst, carry = torch.zeros(B, H, device=dev), torch.zeros(B, H, device=dev)
+
+        def pfwd(t=0, full=False):
+            t = t % T
+            p = peeps if full else [None] * 3
+            C.lstm_peep_fwd_step(W16, h16[t & 1], xg[:, t], cs[t - 1] if t else None, cs[t], hst if full else None,
+                                 out[:, t], h16[(t + 1) & 1], acts[t], p[0], p[1], p[2], mask if full else None,
+                                 (0, 1, 2, 3) if full else (0, 2, 1, 3))
+
+        def pbwd(t=0, full=False):
+            t = t % T
+            p = peeps if full else [None] * 3
+            C.lstm_peep_bwd_step(WT16, dg16[(t + 1) & 1], dout[:, t], None, acts[t], cs[t - 1] if t else None, cs[t],
+                                 dc, carry if full else None, dxg[:, t], dg16[t & 1], p[0], p[1], p[2],
+                                 mask if full else None, (0, 1, 2, 3) if full else (0, 2, 1, 3))
+
+        print(f"peep fwd step (plain)      {timeit(lambda t=0: pfwd(t)):7.2f} us")
+        print(f"peep bwd step (plain)      {timeit(lambda t=0: pbwd(t)):7.2f} us")
+        print(f"peep fwd step (peep+mask)  {timeit(lambda t=0: pfwd(t, True)):7.2f} us")
+        print(f"peep bwd step (peep+mask)  {timeit(lambda t=0: pbwd(t, True)):7.2f} us")
 
 
 if __name__ == "__main__":
