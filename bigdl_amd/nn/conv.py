@@ -285,6 +285,10 @@ class SpatialConvolution(TensorModule):
             x, gy = x.unsqueeze(0), gy.unsqueeze(0)
         H, W = x.shape[2], x.shape[3]
         x, ph, pw, eh, ew = self._prep(x)
+        # set for one call by nn.fusion.residual_backward: the caller takes a compact gradient (ops/conv.py
+        # conv2d_dgrad ``compact``) if this convolution can give one
+        compact = getattr(self, "_dgrad_compact_once", False) and not (squeeze or eh or ew or self.format != "NCHW")
+        self._dgrad_compact_once = False
         if gy.is_cuda:
             gy = self._relu_mask(gy)
             once = getattr(self, "_dgrad_bn_once", False)
@@ -293,7 +297,8 @@ class SpatialConvolution(TensorModule):
             if bn_src is not None and not torch.is_tensor(bn_src[4]):
                 # flag -> the BN's post-ReLU output, which is this conv's input (a tensor there is its sign mask)
                 bn_src = bn_src[:4] + ((input if bn_src[4] else None),)
-            gi = self._dgrad_gpu(x, gy, ph, pw, None if (squeeze or eh or ew or self.format != "NCHW") else bn_src)
+            gi = self._dgrad_gpu(x, gy, ph, pw, None if (squeeze or eh or ew or self.format != "NCHW") else bn_src,
+                                 compact=compact)
         else:
             gy = self._relu_mask(gy)
             gi = torch.nn.grad.conv2d_input(x.shape, self.weight, gy.float(), (self.strideH, self.strideW),
@@ -313,7 +318,7 @@ class SpatialConvolution(TensorModule):
             return ops.relu_bwd_gpu(gy.contiguous(memory_format=CL), self.output)
         return gy * (self.output > 0)
 
-    def _dgrad_gpu(self, x, gy, ph, pw, bn_src=None):
+    def _dgrad_gpu(self, x, gy, ph, pw, bn_src=None, compact=False):
         gy16 = gy if (gy.dtype == BF16 and gy.is_contiguous(memory_format=CL)) else gy.to(BF16, memory_format=CL)
         if self.nGroup == 1:
             w16 = self._w16_padded()
@@ -343,7 +348,8 @@ class SpatialConvolution(TensorModule):
                 bn = {"x": bx, "z": bz, "zm": bzm, "mean": bmean, "aff": baff,
                       "red": bnops.new_stats(Cp, gy16.device)}
             gi = cv.conv2d_dgrad(gy16, wt, xs, (self.strideH, self.strideW), (ph, pw),
-                                 (self.dilationH, self.dilationW), addend=addend, bn=bn, addend_zm=addend_zm)
+                                 (self.dilationH, self.dilationW), addend=addend, bn=bn, addend_zm=addend_zm,
+                                 compact=compact and Cp == x.shape[1])
             if Cp != x.shape[1]:
                 gi = gi[:, : x.shape[1]].contiguous(memory_format=CL)
             elif bn is not None and bn.get("done"):

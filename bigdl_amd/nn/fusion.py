@@ -297,10 +297,45 @@ def _native_det():
     return native.deterministic()
 
 
+def _compact_shortcut_conv(short, first, x):
+    """The 1x1 / stride-s convolution of a ``Sequential(conv, BN)`` projection shortcut when its data gradient can stay
+    compact (ops/conv.py conv2d_dgrad ``compact``: at the convolution's output resolution, none of the zeros between
+    written or read back) because ``first``, the 1x1 / stride-1 head of the branch, adds it as a subsampled addend in
+    its own data-gradient epilogue; None when any link is missing (the gradient is then materialised in full)."""
+    from ..ops import conv as cv
+
+    if not (cv.COMPACT_SHORTCUT[0] and isinstance(short, Sequential) and len(short.modules) == 2):
+        return None
+    sconv, sbn = short.modules
+    if not (isinstance(sconv, SpatialConvolution) and isinstance(sbn, BatchNormalization)
+            and type(sconv).updateGradInput is SpatialConvolution.updateGradInput
+            and type(sconv)._dgrad_gpu is SpatialConvolution._dgrad_gpu
+            and torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+            and x.is_contiguous(memory_format=torch.channels_last)):
+        return None
+
+    def plain_1x1(c, strided):
+        return (c.kernelH == 1 and c.kernelW == 1 and c.padH == 0 and c.padW == 0 and c.nGroup == 1
+                and c.format == "NCHW" and c.propagateBack and not c._frozen
+                and c.nInputPlane == x.shape[1] and c.nInputPlane % 8 == 0 and c.nOutputPlane % 8 == 0
+                and ((c.strideH > 1 and c.strideW > 1) if strided else (c.strideH == 1 and c.strideW == 1)))
+
+    if not (plain_1x1(sconv, True) and plain_1x1(first, False)
+            and type(first)._dgrad_gpu is SpatialConvolution._dgrad_gpu):
+        return None
+    N, C, H, W = x.shape
+    stride = (sconv.strideH, sconv.strideW)
+    # whichever ReLU-mask form the consumer-BN reduction of first's epilogue takes (none, sign mask / affine, bf16 z)
+    if not all(cv.addend_stride_applies(N, first.nOutputPlane, H, W, C, stride, bnm) for bnm in (0, 1, 2)):
+        return None
+    return sconv
+
+
 def residual_backward(seq, x, gradOutput):
     branch, short, bn = seq._residual_plan
     mods = branch.modules
     first = mods[0]
+    sconv = None
     can_fold = (isinstance(first, SpatialConvolution) and first.propagateBack and first.nGroup == 1
                 and first.format == "NCHW" and first.nInputPlane % 8 == 0)
     # identity shortcut: its gradient dres = dz * (y > 0) is never materialised; the block's output gradient and the
@@ -335,9 +370,20 @@ def residual_backward(seq, x, gradOutput):
         if sec is not None:
             dres._bn_red = (sbn, sec[2])
         # shortcut first, so its gradient can be summed inside the epilogue of the branch's first dgrad GEMM
+        sconv = _compact_shortcut_conv(short, first, x) if can_fold else None
+        if sconv is not None:
+            sconv._dgrad_compact_once = True
         gs = short.backward(x, dres)
+        if sconv is not None:
+            sconv._dgrad_compact_once = False
     bn.gradInput = dh
-    fold = masked is not None or (can_fold and gs is not None and gs.dtype == x.dtype and gs.shape == x.shape)
+    from ..ops import conv as cv
+
+    compact = gs is not None and cv.compact_stride(gs) is not None
+    if compact and not (can_fold and sconv is not None and gs.dtype == x.dtype):
+        gs, compact = cv.expand_compact(gs, x.shape[2], x.shape[3]), False      # (not reached: asked for only to fold)
+    fold = masked is not None or (can_fold and gs is not None and gs.dtype == x.dtype
+                                  and (compact or gs.shape == x.shape))
     g = dh
     for i in range(len(mods) - 2, -1, -1):
         inp = mods[i - 1].output if i > 0 else x

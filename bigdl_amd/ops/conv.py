@@ -161,10 +161,49 @@ def dgrad_phases(H, W, R, S, stride, pad, dil):
     return res
 
 
-def conv2d_dgrad(dy, w16t, x_shape, stride, pad, dil=(1, 1), out=None, addend=None, bn=None, addend_zm=None):
+# BIGDL_COMPACT_SHORTCUT (default 1): the data gradient of a ResNet projection shortcut's 1x1 / stride-s convolution
+# stays at the convolution's output resolution (conv2d_dgrad ``compact``) and the first convolution of the branch adds
+# it as a subsampled addend (csrc/kernels.h ConvArgs::add_sh); 0 = written at the input resolution, 3/4 of it zeros
+COMPACT_SHORTCUT = [os.environ.get("BIGDL_COMPACT_SHORTCUT", "1") != "0"]
+
+
+def set_compact_shortcut(on):
+    COMPACT_SHORTCUT[0] = bool(on)
+
+
+def compact_stride(t):
+    """(sh, sw) of a compact data gradient (conv2d_dgrad ``compact``), None for an ordinary tensor."""
+    return getattr(t, "_compact_stride", None)
+
+
+def expand_compact(g, H, W):
+    """A compact data gradient at the (H, W) resolution: its pixels at the stride's multiples, zeros between."""
+    sh, sw = g._compact_stride
+    full = torch.zeros((g.shape[0], g.shape[1], H, W), dtype=g.dtype, device=g.device).contiguous(memory_format=CL)
+    full[:, :, ::sh, ::sw] = g
+    return full
+
+
+def addend_stride_applies(N, K, H, W, C, stride, bn=0):
+    """Does the 1x1 / stride-1 data-gradient GEMM (K -> C channels over N x H x W pixels) take an addend subsampled
+    by ``stride`` (csrc/conv_igemm.hip bigdl_conv_addend_stride_applies)? bn as the binding's."""
+    geo = [N, H, W, K, H, W, 1, 1, K, C, C, H, W, 1, 1, 0, 0]
+    return native.get().conv_addend_stride_applies(geo, [0, 0, 0], stride[0], stride[1], bn)
+
+
+def conv2d_dgrad(dy, w16t, x_shape, stride, pad, dil=(1, 1), out=None, addend=None, bn=None, addend_zm=None,
+                 compact=False):
     """dx = conv_transpose(dy, w) [+ addend]. ``w16t`` is the (C, R, S, K)-ordered transposed weight.
 
-    Stride > 1 runs one dense implicit GEMM per stride phase (no zero-insertion, no masked MFMAs).
+    ``compact`` (1x1, pad 0, stride > 1, no addend / bn / out): dx is returned at the output resolution,
+    (N, C, OH, OW) from one dense GEMM, tagged ``_compact_stride`` = stride: dx[n, :, sh * i, sw * j] of the full
+    gradient, whose other pixels are zero (no fill pass, no strided row map). Ignored for any other convolution.
+    ``addend`` may be such a compact tensor where addend_stride_applies (the caller asks first: the call is refused
+    otherwise, never quietly expanded).
+
+    Stride > 1 runs one dense implicit GEMM per stride phase (no zero-insertion, no masked MFMAs); a 3x3 / stride-2 /
+    pad-1 gradient without addend runs all four phases in one launch where the halo kernel takes it (csrc/conv_halo.hip
+    bigdl_dgrad_s2; BIGDL_DGRAD_S2=0 or native ``set_dgrad_s2(0)`` gives the phase GEMMs).
     ``addend`` (same shape/layout as dx) is summed in the GEMM epilogue — used to fold the residual
     branch gradient of a ResNet block into the block-input gradient.
 
@@ -177,9 +216,23 @@ def conv2d_dgrad(dy, w16t, x_shape, stride, pad, dil=(1, 1), out=None, addend=No
     N, C, H, W = x_shape
     _, K, OH, OW = dy.shape
     R, S = w16t.shape[1], w16t.shape[2]
+    if (compact and R == 1 and S == 1 and tuple(pad) == (0, 0) and (stride[0] > 1 or stride[1] > 1)
+            and out is None and addend is None and bn is None):
+        # every tap lands on the stride's multiples: a dense K -> C GEMM over the OH x OW pixels of dy
+        out = torch.empty((N, C, OH, OW), dtype=BF16, device=dy.device, memory_format=CL)
+        geo = [N, OH, OW, K, OH, OW, 1, 1, K, C, C, OH, OW, 1, 1, 0, 0]
+        native.get().conv_nt(dy, w16t, out, None, None, geo, [0, 0, 0], False, None)
+        out._compact_stride = (int(stride[0]), int(stride[1]))
+        return out
     phases = dgrad_phases(H, W, R, S, stride, pad, dil)
     covered = sum(nI * nJ for (_, _, nI, nJ, _) in phases)
-    if addend is not None and not addend.is_contiguous(memory_format=CL):
+    astride = compact_stride(addend) if addend is not None else None
+    if astride is not None:
+        if (addend_zm is not None or tuple(stride) != (1, 1) or R != 1 or S != 1 or tuple(pad) != (0, 0)
+                or not addend.is_contiguous(memory_format=CL)
+                or tuple(addend.shape) != (N, C, -(-H // astride[0]), -(-W // astride[1]))):
+            raise ValueError("conv2d_dgrad: a compact addend needs a 1x1 / stride-1 data gradient of its geometry")
+    elif addend is not None and not addend.is_contiguous(memory_format=CL):
         addend = addend.contiguous(memory_format=CL)
     if out is None:
         out = torch.empty((N, C, H, W), dtype=BF16, device=dy.device, memory_format=CL)
@@ -204,10 +257,21 @@ def conv2d_dgrad(dy, w16t, x_shape, stride, pad, dil=(1, 1), out=None, addend=No
             and bn["x"].stride() == out.stride() and not native.deterministic():
         bnk = dict(bn_x=bn["x"], bn_z=bn["z"], bn_mean=bn["mean"], bn_aff=bn["aff"], bn_red=bn["red"],
                    bn_zm=bn.get("zm"))
+    if (R == 3 and S == 3 and tuple(stride) == (2, 2) and tuple(pad) == (1, 1) and tuple(dil) == (1, 1)
+            and addend is None and H == 2 * OH and W == 2 * OW and out.is_contiguous(memory_format=CL)
+            and dy.is_contiguous(memory_format=CL) and C_.dgrad_s2(dy, w16t, out, **bnk)):
+        # all four stride phases in one launch from halo tiles of dy (csrc/conv_halo.hip, BIGDL_DGRAD_S2)
+        if bnk:
+            bn["done"] = True
+        return out
+    if bnk:
         bn["done"] = True
     for (a, b, nI, nJ, taps) in phases:
         geo = [N, OH, OW, K, nI, nJ, 1, 1, ldw, C, C, H, W, stride[0], stride[1], a, b]
-        C_.conv_nt(dy, w16t, out, None, None, geo, taps, False, addend, addend_zm=addend_zm, **bnk)
+        if astride is not None:
+            C_.conv_nt(dy, w16t, out, None, None, geo, taps, False, addend, addend_stride=list(astride), **bnk)
+        else:
+            C_.conv_nt(dy, w16t, out, None, None, geo, taps, False, addend, addend_zm=addend_zm, **bnk)
     return out
 
 

@@ -44,7 +44,7 @@ uint8_t* omzm(const OptT& t, int64_t P, int64_t C, const char* n) {
 OptT conv_nt(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT& bias, const OptT& stats,
              std::vector<int64_t> geo, std::vector<int64_t> taps, bool relu, const OptT& addend, const OptT& bn_x,
              const OptT& bn_z, const OptT& bn_mean, const OptT& bn_aff, const OptT& bn_red, bool accumulate,
-             const OptT& bn_zm, const OptT& addend_zm, const OptT& pre) {
+             const OptT& bn_zm, const OptT& addend_zm, const OptT& pre, std::vector<int64_t> addend_stride) {
   TORCH_CHECK(geo.size() == 17 || geo.size() == 18, "conv_nt: bad geometry");
   if (stats && stats->defined())
     TORCH_CHECK(stats->numel() >= BIGDL_STAT_SLOTS * 2 * geo[9], "conv_nt: stats must hold STAT_SLOTS x 2Ncol");
@@ -60,7 +60,9 @@ OptT conv_nt(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
   else a.out = mbf(out, "out");
   a.bias = ocf(bias, "bias"); a.stats = omf(stats, "stats");
   a.addend = ocbf(addend, "addend");
-  if (a.addend) TORCH_CHECK(addend->numel() == out.numel(), "conv_nt: addend must match out");
+  const bool asub = addend_stride.size() == 2 && (addend_stride[0] > 1 || addend_stride[1] > 1);
+  TORCH_CHECK(addend_stride.empty() || addend_stride.size() == 2, "conv_nt: addend_stride is (sh, sw)");
+  if (a.addend && !asub) TORCH_CHECK(addend->numel() == out.numel(), "conv_nt: addend must match out");
   a.bnx = ocbf(bn_x, "bn_x"); a.bnz = ocbf(bn_z, "bn_z"); a.bnmean = ocf(bn_mean, "bn_mean");
   a.bnaff = ocf(bn_aff, "bn_aff"); a.bnred = omf(bn_red, "bn_red");
   a.addzm = nullptr;
@@ -114,6 +116,16 @@ OptT conv_nt(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
   TORCH_CHECK(a.ldo >= a.Ncol && out_avail >= ((int64_t)a.Nb * a.OHo * a.OWo - 1) * a.ldo + a.Ncol,
               "conv_nt: out too small");
   if (a.addend) TORCH_CHECK(a.ldo == a.Ncol, "conv_nt: an addend needs a dense output (ldo == Ncol)");
+  bigdl_conv_addend_stride(&a, 1, 1, 0, 0);
+  if (asub) {
+    // subsampled addend (ConvArgs::add_sh): (Nb, Ncol, ceil(OH / sh), ceil(OW / sw)) channels_last. The caller asks
+    // conv_addend_stride_applies first and materialises the addend itself when no kernel takes it
+    TORCH_CHECK(a.addend && addend->dim() == 4 && addend->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    addend->size(0) == a.Nb && addend->size(1) == a.Ncol, "conv_nt: subsampled addend must be NHWC");
+    bigdl_conv_addend_stride(&a, (int)addend_stride[0], (int)addend_stride[1], (int)addend->size(2),
+                             (int)addend->size(3));
+    TORCH_CHECK(bigdl_conv_addend_stride_applies(&a), "conv_nt: no kernel takes this subsampled addend");
+  }
   TORCH_CHECK((a.OH - 1) * a.omul_h + a.ooff_h < a.OHo && (a.OW - 1) * a.omul_w + a.ooff_w < a.OWo,
               "conv_nt: output placement out of range");
   OptT materialised;
@@ -136,6 +148,69 @@ OptT conv_nt(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
   TORCH_CHECK(rc == 0, "conv_nt: unsupported shape (channels must be a multiple of 8; fp32 output needs Ncol % 8 "
               "== 0 and no fused stats / BN / ReLU / addend)");
   return materialised;
+}
+
+// One-pass data gradient of a 3x3 / stride-2 / pad-1 convolution (bigdl_dgrad_s2): dy (N, K, OH, OW) and dx
+// (N, C, 2 OH, 2 OW) bf16 channels_last (dx may be a channel slice: row stride ldo), wt the (C, 3, 3, K) transposed
+// weight; optional consumer-BN reduction as conv_nt's. Returns false without launching anything when the kernel does
+// not take the call (the caller runs the four phase GEMMs).
+bool dgrad_s2(const Tensor& dy, const Tensor& wt, const Tensor& out, const OptT& bn_x, const OptT& bn_z,
+              const OptT& bn_mean, const OptT& bn_aff, const OptT& bn_red, const OptT& bn_zm) {
+  if (dy.dim() != 4 || out.dim() != 4 || wt.dim() != 4 || !dy.is_contiguous(at::MemoryFormat::ChannelsLast) ||
+      !wt.is_contiguous() || wt.size(1) != 3 || wt.size(2) != 3 || wt.size(3) != dy.size(1) ||
+      wt.size(0) != out.size(1) || out.size(0) != dy.size(0) || out.stride(1) != 1 ||
+      out.scalar_type() != at::kBFloat16 || !out.is_contiguous(at::MemoryFormat::ChannelsLast))
+    return false;
+  ConvArgs a{};
+  a.src = cbf(dy, "dy"); a.wt = cbf(wt, "wt"); a.out = mbf(out, "out");
+  a.Nb = (int)dy.size(0); a.Hs = (int)dy.size(2); a.Ws = (int)dy.size(3); a.Cs = (int)dy.size(1);
+  a.OH = (int)out.size(2); a.OW = (int)out.size(3);
+  a.mul_h = a.mul_w = 1; a.ldw = 9 * a.Cs; a.Ncol = (int)out.size(1); a.ldo = a.Ncol;
+  a.OHo = a.OH; a.OWo = a.OW; a.omul_h = a.omul_w = 1; a.ident_out = 1;
+  a.ntaps = 9; a.Kdim = 9 * a.Cs; a.M = a.Nb * a.OH * a.OW;
+  for (int t = 0; t < 9; ++t) { a.tap_h[t] = (t / 3) == 0; a.tap_w[t] = (t % 3) == 0; a.tap_k[t] = (short)t; }
+  bigdl_conv_addend_stride(&a, 1, 1, 0, 0);
+  a.bnx = ocbf(bn_x, "bn_x"); a.bnz = ocbf(bn_z, "bn_z"); a.bnmean = ocf(bn_mean, "bn_mean");
+  a.bnaff = ocf(bn_aff, "bn_aff"); a.bnred = omf(bn_red, "bn_red");
+  if (bn_zm && bn_zm->defined()) a.bnzm = omzm(bn_zm, out.numel() / a.Ncol, a.Ncol, "bn_zm");
+  if (a.bnred) {
+    TORCH_CHECK(!bigdl_deterministic(), "dgrad_s2: epilogue BN reductions are not deterministic");
+    TORCH_CHECK(a.bnx && a.bnmean && bn_x->numel() == out.numel() && bn_mean->numel() >= a.Ncol &&
+                    (!a.bnaff || bn_aff->numel() >= 2 * a.Ncol) && bn_red->numel() >= BIGDL_STAT_SLOTS * 2 * a.Ncol,
+                "dgrad_s2: bn operands");
+  }
+  if (!bigdl_dgrad_s2_applies(&a)) return false;
+  TORCH_CHECK(bigdl_dgrad_s2(&a, stream()) == 0, "dgrad_s2: launch failed");
+  return true;
+}
+
+// Would conv_nt take an addend subsampled by (sh, sw) for this geometry (conv_nt's geo / taps)? bn: 0 = no consumer-BN
+// reduction, 1 = with a sign-mask or affine ReLU mask, 2 = with a bf16 z mask. No tensors: the native predicate tests
+// pointers for null / alignment only, so present operands are stood in for by an aligned non-null address.
+bool conv_addend_stride_applies(std::vector<int64_t> geo, std::vector<int64_t> taps, int64_t sh, int64_t sw,
+                                int64_t bn) {
+  if (geo.size() != 17 || taps.size() % 3 != 0 || taps.empty() || taps.size() / 3 > CONV_MAX_TAPS) return false;
+  ConvArgs a{};
+  const uint16_t* present = reinterpret_cast<const uint16_t*>(uintptr_t(256));
+  a.src = present; a.wt = present; a.out = const_cast<uint16_t*>(present); a.addend = present;
+  if (bn) {
+    a.bnx = present; a.bnmean = reinterpret_cast<const float*>(present);
+    a.bnred = reinterpret_cast<float*>(const_cast<uint16_t*>(present));
+    if (bn == 2) a.bnz = present;
+  }
+  a.Nb = geo[0]; a.Hs = geo[1]; a.Ws = geo[2]; a.Cs = geo[3]; a.OH = geo[4]; a.OW = geo[5];
+  a.mul_h = geo[6]; a.mul_w = geo[7]; a.ldw = geo[8]; a.Ncol = geo[9]; a.ldo = geo[10];
+  a.OHo = geo[11]; a.OWo = geo[12]; a.omul_h = geo[13]; a.omul_w = geo[14]; a.ooff_h = geo[15]; a.ooff_w = geo[16];
+  a.ntaps = (int)(taps.size() / 3);
+  a.Kdim = a.ntaps * a.Cs;
+  a.M = a.Nb * a.OH * a.OW;
+  a.ident_out = (a.OHo == a.OH && a.OWo == a.OW && a.omul_h == 1 && a.omul_w == 1 && a.ooff_h == 0 && a.ooff_w == 0);
+  for (int t = 0; t < a.ntaps; ++t) {
+    a.tap_h[t] = (short)taps[3 * t]; a.tap_w[t] = (short)taps[3 * t + 1]; a.tap_k[t] = (short)taps[3 * t + 2];
+  }
+  if (sh < 2 || sw < 2 || a.OH < 1 || a.OW < 1) return false;
+  bigdl_conv_addend_stride(&a, (int)sh, (int)sw, (int)((a.OH + sh - 1) / sh), (int)((a.OW + sw - 1) / sw));
+  return bigdl_conv_addend_stride_applies(&a) != 0;
 }
 
 // geo = [Nb, Hs, Ws, Cs, OH, OW, R, S, sh, sw, ph, pw, dh, dw, M, Ncol, Kdim, ldy]
@@ -665,6 +740,8 @@ void conv_i8(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
   a.out = reinterpret_cast<uint16_t*>(out.data_ptr());
   a.bias = ocf(bias, "bias"); a.stats = nullptr; a.addend = nullptr; a.out32 = nullptr; a.accum32 = 0;
   a.ws = nullptr; a.ksplit = 0; a.pstride = 0; a.pre = nullptr;
+  a.OW = a.OH = 0;
+  bigdl_conv_addend_stride(&a, 1, 1, 0, 0);
   a.bnx = nullptr; a.bnz = nullptr; a.bnzm = nullptr; a.addzm = nullptr; a.bnmean = nullptr; a.bnaff = nullptr;
   a.bnred = nullptr;
   a.Nb = geo[0]; a.Hs = geo[1]; a.Ws = geo[2]; a.Cs = geo[3]; a.OH = geo[4]; a.OW = geo[5];
@@ -1550,7 +1627,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("geo"), py::arg("taps"), py::arg("relu"), py::arg("addend") = py::none(), py::arg("bn_x") = py::none(),
         py::arg("bn_z") = py::none(), py::arg("bn_mean") = py::none(), py::arg("bn_aff") = py::none(),
         py::arg("bn_red") = py::none(), py::arg("accumulate") = false, py::arg("bn_zm") = py::none(),
-        py::arg("addend_zm") = py::none(), py::arg("pre") = py::none());
+        py::arg("addend_zm") = py::none(), py::arg("pre") = py::none(),
+        py::arg("addend_stride") = std::vector<int64_t>());
+  m.def("dgrad_s2", &dgrad_s2, py::arg("dy"), py::arg("wt"), py::arg("out"), py::arg("bn_x") = py::none(),
+        py::arg("bn_z") = py::none(), py::arg("bn_mean") = py::none(), py::arg("bn_aff") = py::none(),
+        py::arg("bn_red") = py::none(), py::arg("bn_zm") = py::none());
+  m.def("set_dgrad_s2", &bigdl_set_dgrad_s2);
+  m.def("conv_addend_stride_applies", &conv_addend_stride_applies, py::arg("geo"), py::arg("taps"), py::arg("sh"),
+        py::arg("sw"), py::arg("bn") = 0);
   m.def("conv_wgrad", &conv_wgrad, py::arg("dy"), py::arg("src"), py::arg("dw"), py::arg("dbias"), py::arg("geo"),
         py::arg("pre") = py::none());
   m.def("transpose_krsc", &transpose_krsc);

@@ -18,6 +18,29 @@ struct GemmRowMap {
   }
 };
 
+// Buffer resources of the branch-free epilogues: a row without an operand gets a byte offset past num_records (its
+// loads return 0, its stores are dropped).
+constexpr unsigned EOOB = 0x7ffffff0u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p, size_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)(bytes < 0x7fffffffu ? bytes : 0x7fffffffu),
+                                           0x00020000);
+}
+
+// Subsampled addend (ConvArgs::add_sh > 1, identity output rows): bytes of the whole addend, and the byte offset of
+// the addend granule that output row m = (nb, h, w) adds at channel n — EOOB (reads zeros) for a pixel between the
+// addend's. The divisions are multiply-highs by the host's reciprocals (exact: bigdl_conv_addend_stride_applies
+// bounds M times every divisor below 2^32).
+__device__ __forceinline__ size_t addend_sub_bytes(const ConvArgs& a) {
+  return (((size_t)a.Nb * a.add_H * a.add_W - 1) * a.ldo + a.Ncol) * 2;
+}
+__device__ __forceinline__ unsigned addend_sub_off(const ConvArgs& a, unsigned m, int n) {
+  const unsigned hw = __umulhi(m, a.add_mow), w = m - hw * (unsigned)a.OW;
+  const unsigned nb = __umulhi(hw, a.add_moh), h = hw - nb * (unsigned)a.OH;
+  const unsigned hq = __umulhi(h, a.add_msh), wq = __umulhi(w, a.add_msw);
+  const bool on = hq * (unsigned)a.add_sh == h && wq * (unsigned)a.add_sw == w;
+  return on ? (((nb * a.add_H + hq) * a.add_W + wq) * a.ldo + n) * 2u : EOOB;
+}
+
 // Coalescing epilogue (Ncol % 8 == 0, ldo % 8 == 0): each wave parks its fp32 TM x TN tile in its own
 // slice of the (now idle) staging LDS — [pixel][channel], 16-byte granules XOR-swizzled by pixel so both
 // the 16-byte writes (lanes of 16 consecutive pixels) and the 2 x 16-byte reads (lanes along a pixel row)
@@ -57,6 +80,8 @@ __device__ __forceinline__ void nt_epilogue_lds(const ConvArgs& a, v4f (&acc)[MI
   constexpr int MIH = MI / NH, NRH = NR / NH;
   static_assert(MI % NH == 0 && NR % NH == 0, "row chunks");
   const bool bnw = a.bnred && !a.stats;
+  const bool asub = a.addend && a.add_sh > 1;      // ConvArgs::add_sh (uniform)
+  const __amdgpu_buffer_rsrc_t r_asub = rsrc_of(a.addend, asub ? addend_sub_bytes(a) : 0);
 #pragma unroll
   for (int h = 0; h < NH; ++h) {
   // Phase 1: every global read of the chunk (addend, consumer-BN x / z) is issued before its first store:
@@ -75,8 +100,13 @@ __device__ __forceinline__ void nt_epilogue_lds(const ConvArgs& a, v4f (&acc)[MI
     pz[rr] = v4u{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
     if (orow >= 0) {
       if (a.addend) {
-        pad[rr] = *reinterpret_cast<const v4u*>(a.addend + off);
-        if (a.addzm) pad[rr] &= mask8_to_and(a.addzm[off >> 3]);
+        if (asub) {     // subsampled addend: one load for every row, pixels between the addend's read zeros
+          pad[rr] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(
+                                                r_asub, addend_sub_off(a, (unsigned)orow, n), 0, 0));
+        } else {
+          pad[rr] = *reinterpret_cast<const v4u*>(a.addend + off);
+          if (a.addzm) pad[rr] &= mask8_to_and(a.addzm[off >> 3]);
+        }
       }
       if (bnw) {
         px[rr] = *reinterpret_cast<const v4u*>(a.bnx + off);
@@ -204,17 +234,12 @@ __device__ __forceinline__ void nt_epilogue_lds(const ConvArgs& a, v4f (&acc)[MI
 // its stores, and 7 row chunks per tile serialise on them: 42 of the 79 us of the 28x28 layer, BIGDL_CONV_HALO_ABL)
 // is replaced by two branch-free forms; rows without an output pixel get a buffer offset past num_records (stores
 // dropped, loads return 0).
-constexpr unsigned EOOB = 0x7ffffff0u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)(bytes < 0x7fffffffu ? bytes : 0x7fffffffu),
-                                           0x00020000);
-}
-
 // Workgroup-level commit of per-wave channel sums: every wave parks its 64 channels' (s1, s2) in LDS, then one pass of
 // the workgroup adds the WPX pixel-group partials of each of its KT channels and issues ONE atomic per value: 2 * KT /
 // 256 full-wave atomic instructions per tile instead of 16-32 mostly-idle ones per wave (a memory-side float atomic
 // costs ~50 ns per wave-instruction per CU whatever its lane count: that, not bandwidth, made the epilogue slow).
-template <int WCH, int KT>
+// NTAIL: the channel tile may run past Ncol (Ncol % 8 == 0): those channels commit nothing.
+template <int WCH, int KT, bool NTAIL = false>
 __device__ __forceinline__ void halo_commit(float* red, float* rl, int k0, int Ncol, int bid) {
   __syncthreads();
   const int t = threadIdx.x;
@@ -223,7 +248,8 @@ __device__ __forceinline__ void halo_commit(float* red, float* rl, int k0, int N
     float v = 0.f;
 #pragma unroll
     for (int wp = 0; wp < 4 / WCH; ++wp) v += rl[(wp * WCH + wc) * 128 + which * 64 + cl];
-    atomicAdd(red + (size_t)(bid & (BIGDL_STAT_SLOTS - 1)) * 2 * Ncol + which * Ncol + k0 + c, v);
+    if (!NTAIL || k0 + c < Ncol)
+      atomicAdd(red + (size_t)(bid & (BIGDL_STAT_SLOTS - 1)) * 2 * Ncol + which * Ncol + k0 + c, v);
   }
 }
 
@@ -232,7 +258,9 @@ __device__ __forceinline__ void halo_commit(float* red, float* rl, int k0, int N
 // then 8 lanes store one pixel's whole 128-byte row (16-byte buffer stores); statistics of the rounded output.
 // BNR: also the consumer-BN backward reduction of the rounded output (data gradients; no addend): every BN x row and
 // mask byte of the wave's tile is loaded into registers BEFORE the first store, so no load waits behind a store.
-template <int FM, int FN, int WCH, int KT, bool BNR = false, class RM>
+// NTAIL: the wave's 64 channels may run past Ncol (Ncol % 8 == 0, no bias): granules past it are neither loaded nor
+// stored (out-of-range offsets) and commit nothing.
+template <int FM, int FN, int WCH, int KT, bool BNR = false, bool NTAIL = false, class RM>
 __device__ __forceinline__ void halo_epi_lean(const ConvArgs& a, v4f (&acc)[FM][FN], int vbase, int nbase, int lane,
                                               int bid, unsigned char* sl, const RM& rm, float* rl0, int k0) {
   float* rl = rl0 + (threadIdx.x >> 6) * 128;
@@ -242,7 +270,7 @@ __device__ __forceinline__ void halo_epi_lean(const ConvArgs& a, v4f (&acc)[FM][
 #pragma unroll
   for (int j = 0; j < FN; ++j)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) bs[j][e] = a.bias ? a.bias[nbase + j * 16 + 4 * (lane >> 4) + e] : 0.f;
+    for (int e = 0; e < 4; ++e) bs[j][e] = (a.bias && !NTAIL) ? a.bias[nbase + j * 16 + 4 * (lane >> 4) + e] : 0.f;
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -255,6 +283,7 @@ __device__ __forceinline__ void halo_epi_lean(const ConvArgs& a, v4f (&acc)[FM][
   const size_t rows = (size_t)a.Nb * a.OH * a.OW;
   const __amdgpu_buffer_rsrc_t ro = rsrc_of(a.out, ((rows - 1) * a.ldo + a.Ncol) * 2);
   const int q = lane & 7;
+  const bool cok = !NTAIL || nbase + q * 8 < a.Ncol;       // this lane's 8-channel granule exists
   float s1[8], s2[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
@@ -273,7 +302,7 @@ __device__ __forceinline__ void halo_epi_lean(const ConvArgs& a, v4f (&acc)[FM][
     zmode = a.bnzm ? 1 : a.bnaff ? 3 : 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const int c = nbase + q * 8 + e;
+      const int c = NTAIL ? min(nbase + q * 8 + e, a.Ncol - 1) : nbase + q * 8 + e;
       bmu[e] = a.bnmean[c];
       bsc[e] = a.bnaff ? a.bnaff[c] : 0.f;
       bsh[e] = a.bnaff ? a.bnaff[a.Ncol + c] : 0.f;
@@ -282,9 +311,10 @@ __device__ __forceinline__ void halo_epi_lean(const ConvArgs& a, v4f (&acc)[FM][
     for (int r = 0; r < NRW; ++r) {
       const long orow = rm(a, vbase + r * 8 + (lane >> 3));
       const size_t el = (size_t)(orow >= 0 ? orow : 0) * a.ldo + nbase + q * 8;
-      const unsigned off = orow >= 0 ? (unsigned)(el * 2) : EOOB;
+      const bool on = orow >= 0 && cok;
+      const unsigned off = on ? (unsigned)(el * 2) : EOOB;
       px[r] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rbx, off, 0, 0));
-      zbm[r] = zmode == 1 ? __builtin_amdgcn_raw_buffer_load_b8(rzm, orow >= 0 ? (unsigned)(el >> 3) : EOOB, 0, 0) : 0u;
+      zbm[r] = zmode == 1 ? __builtin_amdgcn_raw_buffer_load_b8(rzm, on ? (unsigned)(el >> 3) : EOOB, 0, 0) : 0u;
     }
   }
 #pragma unroll
@@ -318,7 +348,7 @@ __device__ __forceinline__ void halo_epi_lean(const ConvArgs& a, v4f (&acc)[FM][
         s1[2 * e + 1] += y1; s2[2 * e + 1] += y1 * y1;
       }
     }
-    const unsigned off = orow >= 0 ? (unsigned)(((size_t)orow * a.ldo + nbase + q * 8) * 2) : EOOB;
+    const unsigned off = (orow >= 0 && cok) ? (unsigned)(((size_t)orow * a.ldo + nbase + q * 8) * 2) : EOOB;
     __builtin_amdgcn_raw_buffer_store_b128(o, ro, off, 0, 0);
   }
   if (st || BNR) {          // uniform: every wave of the workgroup takes this branch
@@ -333,7 +363,7 @@ __device__ __forceinline__ void halo_epi_lean(const ConvArgs& a, v4f (&acc)[FM][
 #pragma unroll
       for (int e = 0; e < 8; ++e) { rl[q * 8 + e] = s1[e]; rl[64 + q * 8 + e] = s2[e]; }
     }
-    halo_commit<WCH, KT>(BNR ? a.bnred : a.stats, rl0, k0, a.Ncol, bid);
+    halo_commit<WCH, KT, NTAIL>(BNR ? a.bnred : a.stats, rl0, k0, a.Ncol, bid);
   }
 }
 

@@ -101,6 +101,20 @@ struct HaloRowMap {
   }
 };
 
+// One-pass 3x3 / stride-2 / pad-1 data gradient (conv_halo_kernel S2): virtual pixel (n, i, j) of the dy tile ->
+// output row (n, 2 i + pa, 2 j + pb) of dx for stride phase (pa, pb); a.OH / a.OW are dx's
+template <int W, int RB>
+struct HaloRowMapS2 {
+  int n0, oh0, vend, pa, pb;
+  __device__ __forceinline__ long operator()(const ConvArgs& a, int v) const {
+    constexpr int WP = W + 2;
+    if (v >= vend) return -1;
+    const int vr = v / WP, j = v - vr * WP;
+    if (j < 1 || j > W) return -1;
+    return ((long)n0 * a.OH + 2 * (oh0 + vr) + pa) * a.OW + 2 * (j - 1) + pb;
+  }
+};
+
 // Full form, straight from the accumulators (a lane owns 4 consecutive channels of one pixel per fragment): bias,
 // residual addend (fp32 add before rounding), ReLU, 8-byte stores, BN statistics or the consumer-BN backward reduction
 // of the rounded gradient under the z / sign-mask / affine ReLU mask (nt_epilogue_lds semantics). Every optional
@@ -280,9 +294,16 @@ __device__ __forceinline__ void halo_epi_i8(const ConvArgs& a, const I8Epi& ep, 
 // its own DMA has landed and before the barrier that publishes the chunk; granules of halo / pad rows (out-of-range
 // offsets, read as zeros) are left zero. The per-channel table sits in LDS behind the pipeline buffers.
 constexpr int PRE_MAXC = 512;
-template <int W, int RB, int NIMG, int KT, int WPX, int EPI, int ABL = 0, int EB = 2, bool PRE = false>
+// S2: the one-pass data gradient of a 3x3 / stride-2 / pad-1 convolution. The tile is dy (Hs x Ws = W x W, Cs = the
+// convolution's output channels), staged exactly as above; tap t = 3 r + s (tap_k = t, the (C, R, S, K) weight) reads
+// dy at (i + (r == 0), j + (s == 0)) and belongs to stride phase (r != 1, s != 1) of dx, so the 9 K-steps of a chunk
+// feed four accumulator sets — 1 + 2 + 2 + 4 taps, no step without its MFMAs — and the epilogue runs once per phase
+// with HaloRowMapS2 (lean forms only: EPI 0 / 2, channel tiles may run past Ncol).
+template <int W, int RB, int NIMG, int KT, int WPX, int EPI, int ABL = 0, int EB = 2, bool PRE = false, bool S2 = false>
 __global__ __launch_bounds__(256, 2) void conv_halo_kernel(ConvArgs a, I8Epi ep) {
   static_assert((EB == 1) == (EPI == 3), "int8 operands go with the int8 epilogue");
+  static_assert(!S2 || (NIMG == 1 && EB == 2 && !PRE && ABL == 0 && (EPI == 0 || EPI == 2)), "one-pass stride-2 dgrad");
+  constexpr int NPH = S2 ? 4 : 1;
   static_assert(!PRE || (EB == 2 && EPI == 0), "BN-on-load: bf16 forwards with the lean epilogue");
   constexpr int CH = 64 / EB;                                 // channels per 64-byte chunk row
   using H = HaloF<W, RB, NIMG, KT, WPX>;
@@ -295,7 +316,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(ConvArgs a, I8Epi ep)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wpx = wave / WCH, wch = wave % WCH;
   const int C = a.Cs, IH = a.Hs;
-  const int tiles_n = a.Ncol / KT;
+  const int tiles_n = S2 ? (a.Ncol + KT - 1) / KT : a.Ncol / KT;
   const int segs = IH / RB;                                   // RB < H: segments per image; RB == H: 1
   const int tiles_m = NIMG == 1 ? a.Nb * segs : (a.Nb + NIMG - 1) / NIMG;
   const int nwg = tiles_m * tiles_n;
@@ -436,11 +457,13 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(ConvArgs a, I8Epi ep)
   const int v0 = wpx * H::TM + (lane & 15);
 
   using AccT = std::conditional_t<EB == 1, v4i, v4f>;
-  AccT acc[FM][FN];
+  AccT accp[NPH][FM][FN];
 #pragma unroll
-  for (int i = 0; i < FM; ++i)
+  for (int p = 0; p < NPH; ++p)
 #pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = AccT{0, 0, 0, 0};
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) accp[p][i][j] = AccT{0, 0, 0, 0};
 
   // prologue: chunk 0 and weight steps 0 .. D-1; retire step 0 (younger: steps 1 .. D-1)
   issue_x(0);
@@ -456,6 +479,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(ConvArgs a, I8Epi ep)
     const unsigned xb = lds_base + (unsigned)((ch & 1) * H::XBYTES);
     hfor<9>([&](auto tc) {
       constexpr int t = decltype(tc)::value;
+      constexpr int ph = S2 ? 2 * ((t / 3) != 1) + ((t % 3) != 1) : 0;     // stride phase of tap t
+      auto& acc = accp[ph];
       const int s = ch * 9 + t;
       // slot (s + D) % NSW was read in step s - 1 (retired by the barrier that ended it); x buffer (ch + 1) & 1 was
       // last read by chunk ch - 1
@@ -516,6 +541,19 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(ConvArgs a, I8Epi ep)
     });
   }
 
+  if constexpr (S2) {
+    static_assert(!S2 || 4 * H::TM * 128 + 4 * 128 * 4 <= H::LDS, "bf16 epilogue slices must fit the LDS");
+    hfor<4>([&](auto pc) {
+      constexpr int p = decltype(pc)::value;
+      const HaloRowMapS2<W, RB> rm2{n0, oh0, H::VR * WP, p >> 1, p & 1};
+      if constexpr (p > 0) __syncthreads();        // the previous phase's commit has read the per-wave sums
+      halo_epi_lean<FM, FN, WCH, KT, EPI == 2, true>(a, accp[p], wpx * H::TM, k0 + wch * H::TN, lane, bid,
+                                                     lds + wave * H::TM * 128, rm2,
+                                                     reinterpret_cast<float*>(lds + 4 * H::TM * 128), k0);
+    });
+    return;
+  }
+  auto& acc = accp[0];
   if constexpr (ABL & 1) {
     float t = 0.f;                                 // keep every accumulator (and so every MFMA) alive
 #pragma unroll
@@ -563,6 +601,16 @@ void launch_halo_f(const ConvArgs& a, hipStream_t st) {
   else if (leanbn && g_conv_halo_bn) conv_halo_kernel<W, RB, NIMG, KT, WPX, 2><<<g, b, 0, st>>>(a, I8Epi{});
   else conv_halo_kernel<W, RB, NIMG, KT, WPX, 1><<<g, b, 0, st>>>(a, I8Epi{});
 }
+
+// One-pass stride-2 data gradient: 32-pixel x 64-channel wave tiles (4 phases x 2 x 4 accumulator fragments)
+template <int W, int RB, int KT, int WPX>
+void launch_halo_s2(const ConvArgs& a, hipStream_t st) {
+  const int nwg = a.Nb * (a.Hs / RB) * ((a.Ncol + KT - 1) / KT);
+  if (a.bnred != nullptr) conv_halo_kernel<W, RB, 1, KT, WPX, 2, 0, 2, false, true><<<dim3(nwg), dim3(256), 0, st>>>(a, I8Epi{});
+  else conv_halo_kernel<W, RB, 1, KT, WPX, 0, 0, 2, false, true><<<dim3(nwg), dim3(256), 0, st>>>(a, I8Epi{});
+}
+
+int g_dgrad_s2 = -1;
 
 // ------------------------------------------------------------------------------------------------
 // int8 image stem (7x7 / stride 2 / pad 3, 64 output channels, 224 -> 112) over the width im2col the input quantizer
@@ -800,6 +848,46 @@ int bigdl_conv_halo(const ConvArgs* a, hipStream_t st) {
     case 28: launch_halo_f<28, 7, 1, 128, 2>(*a, st); break;
     case 14: launch_halo_f<14, 14, 1, 128, 2>(*a, st); break;
     case 7: launch_halo_f<7, 7, 3, 128, 2>(*a, st); break;
+    default: return -1;
+  }
+  return 0;
+}
+
+// One-pass 3x3 / stride-2 / pad-1 data gradient (conv_halo_kernel S2). `a`: src = dy (Nb x Hs x Ws x Cs), wt = the
+// (C, 3, 3, K) transposed weight (ldw = 9 Cs), out = dx (Nb x OH x OW x Ncol, OH = 2 Hs), taps t = 3 r + s with
+// tap_h = (r == 0), tap_w = (s == 0), tap_k = t; optional consumer-BN reduction (sign-mask or affine ReLU mask).
+// BIGDL_DGRAD_S2=0 turns it off (the four phase GEMMs of bigdl_conv_nt run instead).
+void bigdl_set_dgrad_s2(int v) { g_dgrad_s2 = v; }
+
+int bigdl_dgrad_s2_applies(const ConvArgs* a) {
+  if (g_dgrad_s2 < 0) {
+    const char* e = getenv("BIGDL_DGRAD_S2");
+    g_dgrad_s2 = e ? atoi(e) : 1;
+  }
+  if (!g_dgrad_s2 || bigdl_get_conv_impl() != 1 || a->ntaps != 9 || a->Kdim != 9 * a->Cs || a->ldw < a->Kdim ||
+      (a->ldw % 8) || (a->Cs % 32) || (a->Ncol % 8) || (a->ldo % 8) || a->ldo < a->Ncol || a->Hs != a->Ws ||
+      a->OH != 2 * a->Hs || a->OW != 2 * a->Ws || !a->ident_out || a->M != a->Nb * a->OH * a->OW || a->Nb < 1)
+    return 0;
+  if (a->Ws != 28 && a->Ws != 14 && a->Ws != 7) return 0;
+  // lean epilogues only: no addend, bias, statistics, fp32 output, BN on load; a BN reduction not under a bf16 z mask
+  if (a->addend || a->addzm || a->bias || a->stats || a->out32 || a->pre || a->relu || a->pstride || a->ws) return 0;
+  if (a->bnred && (!a->bnx || !a->bnmean || (a->bnz && !a->bnzm))) return 0;
+  for (int t = 0; t < 9; ++t)
+    if (a->tap_h[t] != (t / 3 == 0) || a->tap_w[t] != (t % 3 == 0) || a->tap_k[t] != t) return 0;
+  // 32-bit buffer offsets: dy, the weight rows of whole channel tiles, dx's extent
+  if ((size_t)a->Nb * a->Hs * a->Ws * a->Cs * 2 >= (1ull << 31) - (1ull << 20)) return 0;
+  if ((size_t)(a->Ncol + 128) * a->ldw * 2 >= (1ull << 31)) return 0;
+  if (((size_t)(a->M - 1) * a->ldo + a->Ncol) * 2 >= 0x7ff00000ull) return 0;
+  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  return al(a->src) && al(a->wt) && al(a->out) && al(a->bnx);
+}
+
+int bigdl_dgrad_s2(const ConvArgs* a, hipStream_t st) {
+  if (!bigdl_dgrad_s2_applies(a)) return -1;
+  switch (a->Ws) {
+    case 28: launch_halo_s2<28, 4, 64, 4>(*a, st); break;
+    case 14: launch_halo_s2<14, 7, 64, 4>(*a, st); break;
+    case 7: launch_halo_s2<7, 7, 128, 2>(*a, st); break;
     default: return -1;
   }
   return 0;

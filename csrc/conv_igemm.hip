@@ -2308,7 +2308,9 @@ __global__ __launch_bounds__(256, K >= 256 ? 1 : 2) void conv_nt_s1_kernel(ConvA
   // loads carry no branches — branch joins around loads made the compiler drain vmcnt before the stores (328
   // branches, 36 vmcnt(0) in the 64-channel EXT kernel); tail rows store through an out-of-range offset
   const size_t ob = EXT ? ((size_t)(a.M - 1) * a.ldo + a.Ncol) * 2 : 0;
-  const __amdgpu_buffer_rsrc_t r_add = rsrc_of(a.addend, (EXT && a.addend) ? ob : 0);
+  // subsampled addend (ConvArgs::add_sh): its own, smaller resource; pixels between the addend's read zeros
+  const bool asub = EXT && a.addend && a.add_sh > 1;
+  const __amdgpu_buffer_rsrc_t r_add = rsrc_of(a.addend, asub ? addend_sub_bytes(a) : (EXT && a.addend) ? ob : 0);
   const __amdgpu_buffer_rsrc_t r_azm = rsrc_of(a.addzm, (EXT && a.addzm) ? ob / 16 : 0);
   const __amdgpu_buffer_rsrc_t r_bx = rsrc_of(a.bnx, bnw ? ob : 0);
   const __amdgpu_buffer_rsrc_t r_bzm = rsrc_of(a.bnzm, (bnw && a.bnzm) ? ob / 16 : 0);
@@ -2339,7 +2341,8 @@ __global__ __launch_bounds__(256, K >= 256 ? 1 : 2) void conv_nt_s1_kernel(ConvA
         const int m = min(p0 + rr * 8 + (lane >> 3), a.M - 1);
         const size_t off = (size_t)m * a.ldo + n;
         const unsigned eb = (unsigned)(off * 2), zo = (unsigned)(off >> 3);
-        e.pad[rr] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r_add, eb, 0, 0));
+        const unsigned ab = asub ? addend_sub_off(a, (unsigned)m, n) : eb;
+        e.pad[rr] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r_add, ab, 0, 0));
         e.px[rr] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r_bx, eb, 0, 0));
         e.pza[rr] = __builtin_amdgcn_raw_buffer_load_b8(r_azm, zo, 0, 0);     // addend mask
         e.pzz[rr] = __builtin_amdgcn_raw_buffer_load_b8(r_bzm, zo, 0, 0);     // consumer-BN sign mask
@@ -2950,8 +2953,43 @@ int bigdl_conv_pre_applies(const ConvArgs* a) {
   return (s1_applies(a) || bigdl_conv_halo_applies(a)) ? 1 : 0;
 }
 
+void bigdl_conv_addend_stride(ConvArgs* a, int sh, int sw, int add_h, int add_w) {
+  // reciprocal for q = __umulhi(x, r) == x / d, exact while x * d < 2^32 (d >= 2)
+  auto rcp = [](int d) { return d >= 2 ? (unsigned)((1ull << 32) / (unsigned)d) + 1u : 0u; };
+  const bool on = sh > 1 || sw > 1;
+  a->add_sh = on ? sh : 1; a->add_sw = on ? sw : 1;
+  a->add_H = on ? add_h : 0; a->add_W = on ? add_w : 0;
+  a->add_mow = rcp(a->OW); a->add_moh = rcp(a->OH); a->add_msh = rcp(sh); a->add_msw = rcp(sw);
+}
+
+// The subsampled addend lives in the streaming 1x1 EXT epilogue and in nt_epilogue_lds as the multi-stage tile kernel
+// calls it (identity rows): 1 when bigdl_conv_nt's dispatch below ends in one of the two for `a`.
+int bigdl_conv_addend_stride_applies(const ConvArgs* a) {
+  if (!a->addend || a->add_sh < 2 || a->add_sw < 2 || a->addzm || a->out32 || a->pre || a->stats) return 0;
+  if (conv_impl() != 1 || a->Cs % 8 != 0 || a->Kdim != a->ntaps * a->Cs || a->M <= 0 || a->pstride > 0) return 0;
+  if (!a->ident_out || (a->Ncol & 7) || a->ldo != a->Ncol || a->OH < 2 || a->OW < 2) return 0;
+  if (a->add_H != (a->OH + a->add_sh - 1) / a->add_sh || a->add_W != (a->OW + a->add_sw - 1) / a->add_sw) return 0;
+  // exact multiply-high divisions of row numbers, 32-bit byte offsets below the out-of-range offset
+  const unsigned long long dmax = std::max(std::max(a->OH, a->OW), std::max(a->add_sh, a->add_sw));
+  if ((unsigned long long)a->M * dmax >= (1ull << 32)) return 0;
+  if (((size_t)(a->M - 1) * a->ldo + a->Ncol) * 2 >= 0x7ff00000u) return 0;
+  if ((reinterpret_cast<uintptr_t>(a->addend) & 15) != 0) return 0;
+  if (bigdl_stem_fwd_applies(a)) return 0;
+  if (s1_applies(a)) return 1;
+  if (bigdl_conv_halo_applies(a)) return 0;
+  if (sk_pick(a) > 0 || p8_pick(a) != 0 || w8_pick(a) != 0) return 0;
+  const bool fastk = (a->Cs % BK) == 0;
+  static const bool p3auto = [] { const char* e = getenv("BIGDL_CONV_P3AUTO"); return e ? atoi(e) != 0 : true; }();
+  const bool p3_pick = p3auto && a->M <= 50176 && a->Kdim >= 1024;
+  const long p3_tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 127) / 128);
+  return (g4_pick() && (a->Cs % 32 == 0 || (g4_slowk() && a->Kdim % 8 == 0)) &&
+          (g4_pick() == 5 || !(p3_pick && fastk && p3_tiles >= 256))) ? 1 : 0;
+}
+
 int bigdl_conv_nt(const ConvArgs* a, hipStream_t st) {
   if (a->Cs % 8 != 0 || a->Kdim != a->ntaps * a->Cs || a->ntaps < 1 || a->ntaps > CONV_MAX_TAPS) return -1;
+  // a subsampled addend only on the kernels that implement it (the caller materialises it otherwise)
+  if (a->addend && (a->add_sh > 1 || a->add_sw > 1) && !bigdl_conv_addend_stride_applies(a)) return -6;
   if (a->pre) {     // a BN applied on load: only the kernels that implement it (the caller materialises otherwise)
     if (!bigdl_conv_pre_applies(a)) return -5;
     if (s1_applies(a)) launch_s1_any(*a, st);

@@ -53,6 +53,15 @@ struct ConvArgs {
   // padding stays zero — the BN output is never materialised (forward GEMMs of the streaming 1x1 and halo 3x3
   // kernels only: bigdl_conv_pre_applies)
   const float* pre;
+  // Subsampled ("compact") addend: with add_sh > 1 the addend is an [Nb][add_H][add_W][ldo] tensor at 1 / (add_sh,
+  // add_sw) of the output resolution (the data gradient of a 1x1 / stride-s projection shortcut, kept at its own
+  // output resolution) and output pixel (n, h, w) adds addend[n][h / add_sh][w / add_sw] when h % add_sh == 0 and
+  // w % add_sw == 0, else nothing. add_sh <= 1: the addend has the output's placement. Identity output rows only;
+  // add_m* are the multiply-high reciprocals of OW, OH, add_sh, add_sw (bigdl_conv_addend_stride fills them; the
+  // streaming 1x1 EXT epilogue and nt_epilogue_lds on the multi-stage tile kernel implement it:
+  // bigdl_conv_addend_stride_applies)
+  int add_sh, add_sw, add_H, add_W;
+  unsigned add_mow, add_moh, add_msh, add_msw;
 };
 
 // int8 convolution epilogue (quant.hip, conv_halo.hip): dequantize with the per-sample input scale and the per-channel
@@ -95,11 +104,22 @@ void bigdl_colsum_bf16_ld(const uint16_t* x, float* out, long P, int K, long ld,
                           float* det_ws = nullptr);
 // 1 when bigdl_conv_nt can apply a->pre inside the kernel that takes the GEMM (else the caller materialises the source)
 int bigdl_conv_pre_applies(const ConvArgs* a);
+// Subsampled addend (ConvArgs::add_sh): bigdl_conv_addend_stride sets the stride, the addend's pixel geometry and the
+// reciprocals (sh = sw = 1 switches it off); bigdl_conv_addend_stride_applies is 1 when the kernel that bigdl_conv_nt
+// picks for `a` implements it (else the caller materialises the addend at the output resolution; bigdl_conv_nt
+// refuses such a call). Pointers of `a` are only tested for null / alignment.
+void bigdl_conv_addend_stride(ConvArgs* a, int sh, int sw, int add_h, int add_w);
+int bigdl_conv_addend_stride_applies(const ConvArgs* a);
 int bigdl_conv_nt(const ConvArgs* a, hipStream_t st);
 // 3x3 / stride-1 / pad-1 forward or data-gradient GEMM from halo tiles (conv_halo.hip)
 int bigdl_conv_halo_applies(const ConvArgs* a);
 int bigdl_conv_halo(const ConvArgs* a, hipStream_t st);
 void bigdl_set_conv_halo(int v);
+// one-pass 3x3 / stride-2 / pad-1 data gradient from halo tiles of dy, all four stride phases in one launch
+// (conv_halo.hip; BIGDL_DGRAD_S2, default 1)
+int bigdl_dgrad_s2_applies(const ConvArgs* a);
+int bigdl_dgrad_s2(const ConvArgs* a, hipStream_t st);
+void bigdl_set_dgrad_s2(int v);
 // the same on the i8 matrix cores (int8 activations / weights, I8Epi epilogue; no residual addend)
 int bigdl_conv_halo_i8_applies(const ConvArgs* a, const I8Epi* ep);
 int bigdl_conv_halo_i8(const ConvArgs* a, const I8Epi* ep, hipStream_t st);

@@ -49,6 +49,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--hbm", type=float, default=8.0, help="TB/s used for the byte bound")
     ap.add_argument("--json", default="")
+    ap.add_argument("--rows", default="", help="comma-separated shape indices (default: all)")
     a = ap.parse_args()
     N, dev = a.batch, torch.device("cuda")
     CL, BF = torch.channels_last, torch.bfloat16
@@ -58,7 +59,10 @@ def main():
            f"{'us':>8} {'bound_us':>8} {'x_bound':>7} {'TF/s':>6} {'TB/s':>5}")
     print(hdr, flush=True)
     tot = {"fwd": [0.0, 0.0], "dgrad": [0.0, 0.0], "wgrad": [0.0, 0.0]}
+    only = {int(i) for i in a.rows.split(",") if i}
     for si, (C, H, K, R, st, pd, cnt) in enumerate(SHAPES):
+        if only and si not in only:
+            continue
         OH = cv.out_size(H, R, st, pd)
         x = torch.randn(N, C, H, H, device=dev).to(BF, memory_format=CL)
         w = (torch.randn(K, C, R, R, device=dev) * 0.05).to(BF, memory_format=CL)
@@ -72,7 +76,9 @@ def main():
         bx, bw, by = N * H * H * C * 2, K * C * R * R * 2, N * OH * OH * K * 2
         passes = {
             "fwd": (lambda: cv.conv2d_fwd(x, w, bias, (st, st), (pd, pd), stats=stats), bx + bw + by),
-            "dgrad": (lambda: cv.conv2d_dgrad(gy, wt, x.shape, (st, st), (pd, pd)), by + bw + bx),
+            # (a 1x1 / stride-s projection shortcut's gradient stays compact in the step: BIGDL_COMPACT_SHORTCUT)
+            "dgrad": (lambda: cv.conv2d_dgrad(gy, wt, x.shape, (st, st), (pd, pd), compact=cv.COMPACT_SHORTCUT[0]),
+                      by + bw + bx),
             "wgrad": (lambda: cv.conv2d_wgrad(gy, x, dw, db, (st, st), (pd, pd)), by + bx + K * C * R * R * 4),
         }
         if si == 0:
