@@ -1,5 +1,5 @@
 """Fused attention on csrc/attention.hip (forward: online softmax, scores never in HBM; backward: recompute from
-the saved log-sum-exp, dQ via fp32 atomics). q / k / v: [B, H, L, D] fp32 (converted to bf16 MFMA operands),
+the saved row max and log row sum, dQ via fp32 atomics). q / k / v: [B, H, L, D] fp32 (converted to bf16 MFMA operands),
 D = 32, 64, 96 or 128; bias broadcastable to [B, H, Lq, Lk] or a causal mask; attention dropout (reference
 S/nn/Attention.scala:59 ``attentionDropout``) in-kernel: the keep mask is a counter-based hash of (seed, row, key)
 that the backward regenerates, so nothing of size Lq x Lk is ever stored (``dropout_mask`` reproduces it on the
@@ -49,22 +49,25 @@ class _FlashAttention(torch.autograd.Function):
                 b = b.unsqueeze(0)
         o = q.new_empty(B * H, Lq, D, dtype=torch.float32)
         lse = q.new_empty(B * H, Lq, dtype=torch.float32)
-        native.get().attn_fwd(q16, k16, v16, b, H, bool(causal), o, lse, float(dropout_p), int(seed))
-        ctx.save_for_backward(q16, k16, v16, o, lse)
+        # the backward recomputes P from lse's two terms kept apart (row max, log row sum): their fp32 sum loses
+        # log l on rows whose every key is masked with -1e9
+        mlog = q.new_empty(2, B * H, Lq, dtype=torch.float32)
+        native.get().attn_fwd(q16, k16, v16, b, H, bool(causal), o, lse, mlog, float(dropout_p), int(seed))
+        ctx.save_for_backward(q16, k16, v16, o, mlog)
         ctx.bias, ctx.H, ctx.causal, ctx.shape = b, H, bool(causal), (B, H, Lq, Lk, D)
         ctx.drop = (float(dropout_p), int(seed))
         return o.view(B, H, Lq, D)
 
     @staticmethod
     def backward(ctx, do):
-        q16, k16, v16, o, lse = ctx.saved_tensors
+        q16, k16, v16, o, mlog = ctx.saved_tensors
         B, H, Lq, Lk, D = ctx.shape
         do = do.reshape(B * H, Lq, D).float().contiguous()
         dq = torch.zeros(B * H, Lq, D, device=do.device)
         dk = torch.empty(B * H, Lk, D, device=do.device)
         dv = torch.empty(B * H, Lk, D, device=do.device)
         delta = torch.empty(B * H, Lq, device=do.device)
-        native.get().attn_bwd(q16, k16, v16, ctx.bias, ctx.H, ctx.causal, o, lse, do, dq, dk, dv, delta,
+        native.get().attn_bwd(q16, k16, v16, ctx.bias, ctx.H, ctx.causal, o, mlog, do, dq, dk, dv, delta,
                               ctx.drop[0], ctx.drop[1])
         return dq.view(B, H, Lq, D), dk.view(B, H, Lk, D), dv.view(B, H, Lk, D), None, None, None, None
 

@@ -15,8 +15,8 @@ class _LayerNorm(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = x.new_empty(rows)
         rstd = x.new_empty(rows)
-        native.get().layernorm_fwd(x, g.contiguous() if g is not None else None,
-                                   b.contiguous() if b is not None else None, y, mean, rstd, float(eps))
+        g = g.contiguous() if g is not None else None      # the backward reads the same dense gamma
+        native.get().layernorm_fwd(x, g, b.contiguous() if b is not None else None, y, mean, rstd, float(eps))
         ctx.save_for_backward(x, g, mean, rstd)
         ctx.has_b = b is not None
         return y

@@ -6,7 +6,8 @@
 //
 // Layout: Q [BH][Lq][D], K / V [BH][Lk][D] bf16 (q pre-scaled by D^-1/2 as in SplitHeads(mul=true)), D = 32, 64,
 // 96 or 128; bias fp32 broadcast through element strides (sb, sh, sq, sk) over (batch, head, query, key), or causal.
-// Outputs O fp32 [BH][Lq][D] and the row log-sum-exp (fp32 [BH][Lq]) kept for the backward.
+// Outputs O fp32 [BH][Lq][D], the row log-sum-exp (fp32 [BH][Lq]) and, for the backward, its two terms apart
+// (row max and log of the row sum, fp32 [2][BH][Lq]).
 //
 // Forward: workgroup = 64 query rows (4 waves x 16) of one (batch, head); K / V stream through LDS in 64-key
 // tiles. Per tile a wave computes S = Q K^T on v_mfma_f32_16x16x32_bf16 (Q fragments stay in VGPRs), runs the
@@ -14,8 +15,8 @@
 // (bf16) in its own LDS slice to turn the accumulator layout into the A-operand layout, and accumulates P V
 // against V^T (transposed when the tile is staged) — all in fp32 accumulators.
 // Backward (one workgroup per 64-key block, looping over query blocks): P is recomputed from the saved
-// log-sum-exp; dV += P^T dO, dP = dO V^T, dS = P (dP - rowsum(dO o O)), dK += dS^T Q accumulate in VGPRs; dQ +=
-// dS K is accumulated across key blocks with fp32 atomics.
+// row max and log l (P = exp((S - m) - log l)); dV += P^T dO, dP = dO V^T, dS = P (dP - rowsum(dO o O)),
+// dK += dS^T Q accumulate in VGPRs; dQ += dS K is accumulated across key blocks with fp32 atomics.
 #include "common.h"
 #include "kernels.h"
 
@@ -32,6 +33,7 @@ struct AttnArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v;
   const float* bias; long sb, sh, sq, sk;
   float* o; float* lse;
+  float* mlog;                        // [2][BH][Lq]: row max m and log l (lse = m + log l, kept apart)
   const float* dout;                  // backward: dO fp32 [BH][Lq][D]
   const float* delta;                 // backward: rowsum(dO o O) [BH][Lq]
   float* dq; float* dk; float* dv;    // backward outputs fp32
@@ -202,7 +204,16 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
     float* orow = a.o + ((long)bh * a.Lq + qi) * D;
 #pragma unroll
     for (int c = 0; c < NC; ++c) orow[16 * c + col] = oacc[c][i] * inv;
-    if (col == 0) a.lse[(long)bh * a.Lq + qi] = l[i] > 0.f ? m[i] + __logf(l[i]) : NEG_BIG;
+    if (col == 0) {
+      // lse = m + log l is the public value; the backward gets the two terms apart, because a row whose every key
+      // carries a -1e9 mask has m = -1e9, where fp32 (spacing 64) absorbs log l and exp(x - lse) would be 1, not
+      // 1 / l. A fully masked row (l == 0) stores log l = +inf, so the backward's exp gives 0 for any score.
+      const long row = (long)bh * a.Lq + qi;
+      const float logl = l[i] > 0.f ? __logf(l[i]) : INFINITY;
+      a.lse[row] = l[i] > 0.f ? m[i] + logl : NEG_BIG;
+      a.mlog[row] = l[i] > 0.f ? m[i] : 0.f;
+      a.mlog[(long)gridDim.y * a.Lq + row] = logl;
+    }
   }
 }
 
@@ -221,7 +232,7 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) bf16_t sKt[D * AT_BK];     // K^T of this key block [d][key]
   __shared__ __attribute__((aligned(16))) bf16_t sT[4][16 * AT_BK];  // per-wave scratch (P^T / dS^T as A operand)
   __shared__ __attribute__((aligned(16))) bf16_t sdS[AT_BK * AT_BK]; // dS [q][key] for the dQ GEMM
-  __shared__ float sL[AT_BK], sDel[AT_BK];
+  __shared__ float sM[AT_BK], sL[AT_BK], sDel[AT_BK];   // row max, log l, delta of the query block
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int grp = lane >> 4, col = lane & 15;
   const int bh = blockIdx.y, k0 = blockIdx.x * AT_BK, kw = k0 + wave * 16;
@@ -266,7 +277,8 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(AttnArgs a) {
     }
     if (threadIdx.x < AT_BK) {
       const int qi = q0 + threadIdx.x;
-      sL[threadIdx.x] = qi < a.Lq ? a.lse[(long)bh * a.Lq + qi] : 0.f;
+      sM[threadIdx.x] = qi < a.Lq ? a.mlog[(long)bh * a.Lq + qi] : 0.f;
+      sL[threadIdx.x] = qi < a.Lq ? a.mlog[((long)gridDim.y + bh) * a.Lq + qi] : 0.f;
       sDel[threadIdx.x] = qi < a.Lq ? a.delta[(long)bh * a.Lq + qi] : 0.f;
     }
     __syncthreads();
@@ -296,7 +308,7 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(AttnArgs a) {
         const int kj = kw + 4 * grp + i;
         float p = 0.f;
         if (qi < a.Lq && kj < a.Lk && !(a.causal && kj > qi))
-          p = __expf(st[j][i] + bias_at(a, bh, qi, kj) - sL[16 * j + col]);
+          p = __expf((st[j][i] + bias_at(a, bh, qi, kj) - sM[16 * j + col]) - sL[16 * j + col]);
         st[j][i] = p;
         dm[j][i] = a.drop_thr ? drop_mul(a, row, kj) : 1.f;
         T[(4 * grp + i) * AT_BK + 16 * j + col] = f2bf(p * dm[j][i]);
@@ -372,7 +384,7 @@ __global__ void attn_delta_kernel(const float* __restrict__ dout, const float* _
 static AttnArgs to_args(const AttnCall* c) {
   AttnArgs a;
   a.q = c->q; a.k = c->k; a.v = c->v; a.bias = c->bias; a.sb = c->sb; a.sh = c->sh; a.sq = c->sq; a.sk = c->sk;
-  a.o = c->o; a.lse = c->lse; a.dout = c->dout; a.delta = c->delta; a.dq = c->dq; a.dk = c->dk; a.dv = c->dv;
+  a.o = c->o; a.lse = c->lse; a.mlog = c->mlog; a.dout = c->dout; a.delta = c->delta; a.dq = c->dq; a.dk = c->dk; a.dv = c->dv;
   a.H = c->H; a.Lq = c->Lq; a.Lk = c->Lk; a.causal = c->causal;
   const double p = c->drop_p;
   a.drop_thr = p > 0.0 ? (unsigned)fmin(4294967295.0, p * 4294967296.0) : 0u;

@@ -1477,7 +1477,7 @@ void layernorm_bwd(const Tensor& dy, const Tensor& x, const OptT& g, const Tenso
   const int64_t D = x.size(-1), rows = x.numel() / D;
   TORCH_CHECK(mean.numel() == rows && rstd.numel() == rows, "layernorm_bwd: mean/rstd");
   if (dx && dx->defined()) TORCH_CHECK(dx->is_contiguous() && dx->numel() == x.numel(), "layernorm_bwd: dx");
-  if (g && g->defined()) TORCH_CHECK(g->numel() == D, "layernorm_bwd: gamma");
+  if (g && g->defined()) TORCH_CHECK(g->numel() == D && g->is_contiguous(), "layernorm_bwd: gamma");
   if (dg && dg->defined()) TORCH_CHECK(dg->numel() == D && dg->is_contiguous(), "layernorm_bwd: dgamma");
   if (db && db->defined()) TORCH_CHECK(db->numel() == D && db->is_contiguous(), "layernorm_bwd: dbeta");
   TORCH_CHECK(bigdl_layernorm_bwd(cf(dy, "dy"), cf(x, "x"), ocf(g, "g"), cf(mean, "mean"), cf(rstd, "rstd"),
@@ -1507,16 +1507,18 @@ AttnCall attn_call(const Tensor& q, const Tensor& k, const Tensor& v, const OptT
   return c;
 }
 void attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const OptT& bias, int64_t H, bool causal,
-              const Tensor& o, const Tensor& lse, double drop_p, int64_t seed) {
+              const Tensor& o, const Tensor& lse, const Tensor& mlog, double drop_p, int64_t seed) {
   AttnCall c = attn_call(q, k, v, bias, H, causal);
   TORCH_CHECK(drop_p >= 0.0 && drop_p < 1.0, "attention: dropout probability in [0, 1)");
   c.drop_p = (float)drop_p; c.seed = (unsigned long long)seed;
   TORCH_CHECK(o.is_contiguous() && o.numel() == q.numel() && lse.numel() == (int64_t)c.BH * c.Lq, "attn_fwd: o/lse");
-  c.o = mf(o, "o"); c.lse = mf(lse, "lse");
+  TORCH_CHECK(mlog.is_contiguous() && mlog.numel() == 2 * (int64_t)c.BH * c.Lq,
+              "attn_fwd: mlog must hold [2, B*H, Lq] (row max, log row sum)");
+  c.o = mf(o, "o"); c.lse = mf(lse, "lse"); c.mlog = mf(mlog, "mlog");
   TORCH_CHECK(bigdl_attn_fwd(&c, stream()) == 0, "attn_fwd: unsupported shape");
 }
 void attn_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const OptT& bias, int64_t H, bool causal,
-              const Tensor& o, const Tensor& lse, const Tensor& dout, const Tensor& dq, const Tensor& dk,
+              const Tensor& o, const Tensor& mlog, const Tensor& dout, const Tensor& dq, const Tensor& dk,
               const Tensor& dv, const Tensor& delta_ws, double drop_p, int64_t seed) {
   AttnCall c = attn_call(q, k, v, bias, H, causal);
   TORCH_CHECK(drop_p >= 0.0 && drop_p < 1.0, "attention: dropout probability in [0, 1)");
@@ -1525,8 +1527,9 @@ void attn_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const OptT& bia
               "attn_bwd: o/dout");
   TORCH_CHECK(dq.is_contiguous() && dq.numel() == q.numel() && dk.numel() == k.numel() && dv.numel() == v.numel() &&
               dk.is_contiguous() && dv.is_contiguous(), "attn_bwd: gradient buffers");
-  TORCH_CHECK(lse.numel() == (int64_t)c.BH * c.Lq && delta_ws.numel() == (int64_t)c.BH * c.Lq, "attn_bwd: lse/delta");
-  c.o = mf(o, "o"); c.lse = mf(lse, "lse"); c.dout = cf(dout, "dout");
+  TORCH_CHECK(mlog.is_contiguous() && mlog.numel() == 2 * (int64_t)c.BH * c.Lq &&
+              delta_ws.numel() == (int64_t)c.BH * c.Lq, "attn_bwd: mlog/delta");
+  c.o = mf(o, "o"); c.mlog = mf(mlog, "mlog"); c.dout = cf(dout, "dout");
   c.dq = mf(dq, "dq"); c.dk = mf(dk, "dk"); c.dv = mf(dv, "dv");
   TORCH_CHECK(bigdl_attn_bwd(&c, mf(delta_ws, "delta"), stream()) == 0, "attn_bwd: unsupported shape");
 }
@@ -1759,10 +1762,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ones_col_acc", &ones_col_acc);
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"), py::arg("H"),
-        py::arg("causal"), py::arg("o"), py::arg("lse"), py::arg("drop_p") = 0.0, py::arg("seed") = 0);
+        py::arg("causal"), py::arg("o"), py::arg("lse"), py::arg("mlog"), py::arg("drop_p") = 0.0, py::arg("seed") = 0);
   m.def("gconv", &gconv);
   m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"), py::arg("H"),
-        py::arg("causal"), py::arg("o"), py::arg("lse"), py::arg("dout"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
+        py::arg("causal"), py::arg("o"), py::arg("mlog"), py::arg("dout"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
         py::arg("delta_ws"), py::arg("drop_p") = 0.0, py::arg("seed") = 0);
   m.def("layernorm_bwd", &layernorm_bwd);
   m.def("gru_step", &gru_step, py::arg("mode"), py::arg("A"), py::arg("W"), py::arg("B"), py::arg("H"),

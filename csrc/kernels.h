@@ -418,11 +418,12 @@ int bigdl_layernorm_bwd(const float* dy, const float* x, const float* g, const f
                         float* dx, float* dg, float* db, long rows, int D, hipStream_t st);
 
 // Fused attention (csrc/attention.hip). q/k/v bf16 [BH][L][D] (D = 32, 64, 96 or 128), bias fp32 through element
-// strides (sb, sh, sq, sk) or nullptr, o / dq / dk / dv / dout fp32, lse / delta fp32 [BH][Lq]; attention dropout
+// strides (sb, sh, sq, sk) or nullptr, o / dq / dk / dv / dout fp32, lse / delta fp32 [BH][Lq] (lse is an output only); attention dropout
 // with probability drop_p (0: none) from a counter-based hash of (seed, row, key), regenerated by the backward.
 typedef struct {
   const uint16_t* q; const uint16_t* k; const uint16_t* v; const float* bias; long sb, sh, sq, sk;
   float* o; float* lse; const float* dout; const float* delta; float* dq; float* dk; float* dv;
+  float* mlog;   // fp32 [2][BH][Lq]: row max and log row sum (lse's two terms), written by fwd, read by bwd
   int BH, H, Lq, Lk, D, causal;
   float drop_p; unsigned long long seed;
 } AttnCall;
