@@ -18,7 +18,7 @@ loop entirely: a sequence-level autograd Function runs ``h @ U^T`` (library GEMM
 (csrc/elementwise.hip lstm_fwd_kernel / lstm_bwd_kernel: all four gate nonlinearities, the cell update and
 the gradient of both in one pass) per step, and computes dU with ONE [4H, T*B] x [T*B, H] GEMM after the
 reverse sweep instead of T small ones. LSTMPeephole (p == 0) and the maskZero LSTM take the same shape of path on
-the GPU (``_LSTMPeepSeq``: csrc/lstm_peephole.hip, one fused launch per step with peephole terms and a row mask in
+the GPU (``_LSTMPeepSeq``: csrc/lstm.hip, one fused launch per step with peephole terms and a row mask in
 the cell epilogue); every other masked cell runs the generic loop.
 """
 import os
@@ -495,7 +495,7 @@ class _LSTMPeepSeq(torch.autograd.Function):
     maskZero semantics) and a gate layout: ``order`` = positions of the i, f, g, o blocks in the [4H] gate axis of xg
     and U ((0, 2, 1, 3) for nn.LSTM, (0, 1, 2, 3) for nn.LSTMPeephole).
 
-    GPU (fp32 xg, H % 32 == 0): one fused launch per step and direction (csrc/lstm_peephole.hip), the recurrent weight
+    GPU (fp32 xg, H % 32 == 0): one fused launch per step and direction (csrc/lstm.hip), the recurrent weight
     gradient as one native GEMM after the sweep, the peephole gradients by a fixed-order reduction kernel. Other
     tensors: the same forward and the same hand-derived backward in plain torch, in the tensors' own dtype (the
     modules do not route the CPU engine here; it keeps the formulas checkable in fp64)."""
@@ -538,8 +538,8 @@ class _LSTMPeepSeq(torch.autograd.Function):
             hst = h0.contiguous().clone() if mt is not None else None
             c_prev = c0.contiguous()
             for t in range(T):
-                C.lstm_peep_fwd_step(W16, h16[t], xg[:, t], c_prev, cs[t], hst, out[:, t], h16[t + 1], acts[t],
-                                     ps[0], ps[1], ps[2], mt[t] if mt is not None else None, order)
+                C.lstm_fwd_step(W16, h16[t], xg[:, t], c_prev, cs[t], out[:, t], h16[t + 1], acts[t], h_state=hst,
+                                pI=ps[0], pF=ps[1], pO=ps[2], mask=mt[t] if mt is not None else None, order=order)
                 c_prev = cs[t]
             ctx.save_for_backward(c0, U, cs, acts, h16, W16, mt, *ps)
             return out, (hst if hst is not None else out[:, -1].clone()), cs[-1].clone()
@@ -593,10 +593,10 @@ class _LSTMPeepSeq(torch.autograd.Function):
             dhT = None
         c0 = c0.contiguous()
         for t in range(T - 1, -1, -1):
-            C.lstm_peep_bwd_step(WT16, dg16[t + 1] if t < T - 1 else None,
-                                 dout[:, t] if dout is not None else None, dhT if t == T - 1 else None, acts[t],
-                                 cs[t - 1] if t > 0 else c0, cs[t], dc, carry, dxg[:, t], dg16[t], pI, pF, pO,
-                                 mt[t] if mt is not None else None, order)
+            C.lstm_bwd_step(WT16, dg16[t + 1] if t < T - 1 else None,
+                            dout[:, t] if dout is not None else None, dhT if t == T - 1 else None, acts[t],
+                            cs[t - 1] if t > 0 else c0, cs[t], dc, dxg[:, t], dg16[t], carry=carry, pI=pI, pF=pF, pO=pO,
+                            mask=mt[t] if mt is not None else None, order=order)
         dh0, dU = _rnn_param_grads(dg16, h16, U, WT16)
         if carry is not None:
             dh0 = dh0 + carry
@@ -932,7 +932,7 @@ class LSTM(Cell):
             out, h, c = _LSTMSeq.apply(x2.contiguous(), hid[0], hid[1], self.h2g.weight, self._grad_sink(self.h2g))
             return out, [h, c]
         if mask is not None and self._fused_ok() and _LSTMPeepSeq.usable(x2, self.hiddenSize):
-            # maskZero on the GPU: the masked step kernels (csrc/lstm_peephole.hip), no peepholes
+            # maskZero on the GPU: the masked step kernels (csrc/lstm.hip), no peepholes
             out, h, c = _LSTMPeepSeq.apply(x2, hid[0], hid[1], self.h2g.weight, None, None, None, mask,
                                            _LSTMPeepSeq.ORDER_LSTM)
             return out, [h, c]
@@ -979,7 +979,7 @@ class LSTMPeephole(Cell):
 
     def sequence(self, x2, hid, mask=None):
         if self.p == 0 and _LSTMPeepSeq.usable(x2, self.hiddenSize):
-            # GPU: one fused step kernel per time step and direction (csrc/lstm_peephole.hip), with or without a mask
+            # GPU: one fused step kernel per time step and direction (csrc/lstm.hip), with or without a mask
             out, h, c = _LSTMPeepSeq.apply(x2, hid[0], hid[1], self.h2g.weight, self.peepI.weight, self.peepF.weight,
                                            self.peepO.weight, mask, _LSTMPeepSeq.ORDER_PEEPHOLE)
             return out, [h, c]

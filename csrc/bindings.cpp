@@ -1219,41 +1219,7 @@ int64_t rowstride(const Tensor& t, int64_t inner, const char* n) {
   TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.size(1) == inner, n, ": expected [B, ", inner, "] with unit inner stride");
   return t.stride(0);
 }
-void lstm_fwd_step(const Tensor& W16, const OptT& h16_prev, const Tensor& xg, const OptT& c_prev, const Tensor& c_out,
-                   const Tensor& h_out, const Tensor& h16_out, const Tensor& acts) {
-  const int64_t B = xg.size(0), H = W16.size(1);
-  TORCH_CHECK(W16.size(0) == 4 * H && W16.is_contiguous(), "lstm_fwd_step: W16 must be [4H, H] contiguous");
-  TORCH_CHECK(H % 32 == 0, "lstm_fwd_step: H must be a multiple of 32");
-  const int64_t ldx = rowstride(xg, 4 * H, "xg"), ldh = rowstride(h_out, H, "h_out"), lda = rowstride(acts, 4 * H, "acts");
-  TORCH_CHECK(h_out.size(0) == B && acts.size(0) == B && c_out.numel() == B * H && h16_out.numel() == B * H,
-              "lstm_fwd_step: batch mismatch");
-  TORCH_CHECK(c_out.is_contiguous() && h16_out.is_contiguous(), "lstm_fwd_step: c_out/h16_out contiguous");
-  if (h16_prev && h16_prev->defined()) TORCH_CHECK(h16_prev->numel() == B * H && h16_prev->is_contiguous(), "h16_prev");
-  if (c_prev && c_prev->defined()) TORCH_CHECK(c_prev->numel() == B * H && c_prev->is_contiguous(), "c_prev");
-  bigdl_lstm_fwd_step(cbf(W16, "W16"), ocbf(h16_prev, "h16_prev"), cf(xg, "xg"), ldx, ocf(c_prev, "c_prev"),
-                      mf(c_out, "c_out"), mf(h_out, "h_out"), ldh, mbf(h16_out, "h16_out"), mf(acts, "acts"), lda, B, H,
-                      stream());
-}
-void lstm_bwd_step(const Tensor& WT16, const OptT& dg16_next, const OptT& dout, const OptT& dh_ext, const Tensor& acts,
-                   const OptT& c_prev, const Tensor& c_t, const Tensor& dc, const Tensor& dg_out, const Tensor& dg16_out) {
-  const int64_t H = WT16.size(0), B = acts.size(0);
-  TORCH_CHECK(WT16.size(1) == 4 * H && WT16.is_contiguous(), "lstm_bwd_step: WT16 must be [H, 4H] contiguous");
-  TORCH_CHECK(H % 32 == 0, "lstm_bwd_step: H must be a multiple of 32");
-  const int64_t lda = rowstride(acts, 4 * H, "acts"), ldg = rowstride(dg_out, 4 * H, "dg_out");
-  int64_t ldd = 0;
-  if (dout && dout->defined()) { ldd = rowstride(*dout, H, "dout"); TORCH_CHECK(dout->size(0) == B, "dout batch"); }
-  TORCH_CHECK(dg_out.size(0) == B && c_t.numel() == B * H && dc.numel() == B * H && dg16_out.numel() == B * 4 * H,
-              "lstm_bwd_step: batch mismatch");
-  TORCH_CHECK(c_t.is_contiguous() && dc.is_contiguous() && dg16_out.is_contiguous(), "lstm_bwd_step: contiguity");
-  if (dg16_next && dg16_next->defined()) TORCH_CHECK(dg16_next->numel() == B * 4 * H && dg16_next->is_contiguous(), "dg16_next");
-  if (dh_ext && dh_ext->defined()) TORCH_CHECK(dh_ext->numel() == B * H && dh_ext->is_contiguous(), "dh_ext");
-  if (c_prev && c_prev->defined()) TORCH_CHECK(c_prev->numel() == B * H && c_prev->is_contiguous(), "c_prev");
-  bigdl_lstm_bwd_step(cbf(WT16, "WT16"), ocbf(dg16_next, "dg16_next"), ocf(dout, "dout"), ldd, ocf(dh_ext, "dh_ext"),
-                      cf(acts, "acts"), lda, ocf(c_prev, "c_prev"), cf(c_t, "c_t"), mf(dc, "dc"), mf(dg_out, "dg_out"),
-                      ldg, mbf(dg16_out, "dg16_out"), B, H, stream());
-}
-
-// Fused LSTM steps with optional peepholes / row mask and a gate layout (csrc/lstm_peephole.hip). order = positions of
+// Optional peepholes / row mask and the gate layout of the fused LSTM steps (csrc/lstm.hip). order = positions of
 // the i, f, g, o blocks in the [4H] gate axis; pI / pF / pO fp32 [H], all or none; mask = this step's [B] uint8 or bool.
 struct PeepArgs {
   const float *pI = nullptr, *pF = nullptr, *pO = nullptr;
@@ -1286,56 +1252,53 @@ PeepArgs peep_args(const char* fn, const OptT& pI, const OptT& pF, const OptT& p
   TORCH_CHECK(seen == 15, fn, ": gate positions must be a permutation of 0..3");
   return a;
 }
-void lstm_peep_fwd_step(const Tensor& W16, const OptT& h16_prev, const Tensor& xg, const OptT& c_prev,
-                        const Tensor& c_out, const OptT& h_state, const Tensor& h_out, const Tensor& h16_out,
-                        const Tensor& acts, const OptT& pI, const OptT& pF, const OptT& pO, const OptT& mask,
-                        const std::vector<int64_t>& order) {
+// Positional arguments: the unmasked nn.LSTM step; the rest are keywords (none / nn.LSTM's layout by default).
+void lstm_fwd_step(const Tensor& W16, const OptT& h16_prev, const Tensor& xg, const OptT& c_prev, const Tensor& c_out,
+                   const Tensor& h_out, const Tensor& h16_out, const Tensor& acts, const OptT& h_state, const OptT& pI,
+                   const OptT& pF, const OptT& pO, const OptT& mask, const std::vector<int64_t>& order) {
   const int64_t B = xg.size(0), H = W16.size(1);
-  TORCH_CHECK(W16.dim() == 2 && W16.size(0) == 4 * H && W16.is_contiguous(),
-              "lstm_peep_fwd_step: W16 must be [4H, H] contiguous");
-  TORCH_CHECK(H > 0 && H % 32 == 0 && B >= 1, "lstm_peep_fwd_step: H must be a multiple of 32, B >= 1");
+  TORCH_CHECK(W16.dim() == 2 && W16.size(0) == 4 * H && W16.is_contiguous(), "lstm_fwd_step: W16 must be [4H, H] contiguous");
+  TORCH_CHECK(H > 0 && H % 32 == 0 && B >= 1, "lstm_fwd_step: H must be a multiple of 32, B >= 1");
   const int64_t ldx = rowstride(xg, 4 * H, "xg"), ldh = rowstride(h_out, H, "h_out"), lda = rowstride(acts, 4 * H, "acts");
   TORCH_CHECK(h_out.size(0) == B && acts.size(0) == B && c_out.numel() == B * H && h16_out.numel() == B * H,
-              "lstm_peep_fwd_step: batch mismatch");
-  TORCH_CHECK(c_out.is_contiguous() && h16_out.is_contiguous(), "lstm_peep_fwd_step: c_out/h16_out contiguous");
+              "lstm_fwd_step: batch mismatch");
+  TORCH_CHECK(c_out.is_contiguous() && h16_out.is_contiguous(), "lstm_fwd_step: c_out/h16_out contiguous");
   if (h16_prev && h16_prev->defined()) TORCH_CHECK(h16_prev->numel() == B * H && h16_prev->is_contiguous(), "h16_prev");
   if (c_prev && c_prev->defined()) TORCH_CHECK(c_prev->numel() == B * H && c_prev->is_contiguous(), "c_prev");
   if (h_state && h_state->defined()) TORCH_CHECK(h_state->numel() == B * H && h_state->is_contiguous(), "h_state");
-  const PeepArgs a = peep_args("lstm_peep_fwd_step", pI, pF, pO, mask, order, B, H);
-  const int rc = bigdl_lstm_peep_fwd_step(cbf(W16, "W16"), ocbf(h16_prev, "h16_prev"), cf(xg, "xg"), ldx,
-                                          ocf(c_prev, "c_prev"), mf(c_out, "c_out"), omf(h_state, "h_state"),
-                                          mf(h_out, "h_out"), ldh, mbf(h16_out, "h16_out"), mf(acts, "acts"), lda,
-                                          a.pI, a.pF, a.pO, a.mask, a.g[0], a.g[1], a.g[2], a.g[3], (int)B, (int)H,
-                                          stream());
-  TORCH_CHECK(rc == 0, "lstm_peep_fwd_step: unsupported arguments");
+  const PeepArgs a = peep_args("lstm_fwd_step", pI, pF, pO, mask, order, B, H);
+  const int rc = bigdl_lstm_fwd_step(cbf(W16, "W16"), ocbf(h16_prev, "h16_prev"), cf(xg, "xg"), ldx,
+                                     ocf(c_prev, "c_prev"), mf(c_out, "c_out"), omf(h_state, "h_state"),
+                                     mf(h_out, "h_out"), ldh, mbf(h16_out, "h16_out"), mf(acts, "acts"), lda, a.pI,
+                                     a.pF, a.pO, a.mask, a.g[0], a.g[1], a.g[2], a.g[3], (int)B, (int)H, stream());
+  TORCH_CHECK(rc == 0, "lstm_fwd_step: unsupported arguments");
 }
-void lstm_peep_bwd_step(const Tensor& WT16, const OptT& dg16_next, const OptT& dout, const OptT& dh_ext,
-                        const Tensor& acts, const OptT& c_prev, const Tensor& c_t, const Tensor& dc, const OptT& carry,
-                        const Tensor& dg_out, const Tensor& dg16_out, const OptT& pI, const OptT& pF, const OptT& pO,
-                        const OptT& mask, const std::vector<int64_t>& order) {
+void lstm_bwd_step(const Tensor& WT16, const OptT& dg16_next, const OptT& dout, const OptT& dh_ext, const Tensor& acts,
+                   const OptT& c_prev, const Tensor& c_t, const Tensor& dc, const Tensor& dg_out, const Tensor& dg16_out,
+                   const OptT& carry, const OptT& pI, const OptT& pF, const OptT& pO, const OptT& mask,
+                   const std::vector<int64_t>& order) {
   const int64_t H = WT16.size(0), B = acts.size(0);
-  TORCH_CHECK(WT16.dim() == 2 && WT16.size(1) == 4 * H && WT16.is_contiguous(),
-              "lstm_peep_bwd_step: WT16 must be [H, 4H] contiguous");
-  TORCH_CHECK(H > 0 && H % 32 == 0 && B >= 1, "lstm_peep_bwd_step: H must be a multiple of 32, B >= 1");
+  TORCH_CHECK(WT16.dim() == 2 && WT16.size(1) == 4 * H && WT16.is_contiguous(), "lstm_bwd_step: WT16 must be [H, 4H] contiguous");
+  TORCH_CHECK(H > 0 && H % 32 == 0 && B >= 1, "lstm_bwd_step: H must be a multiple of 32, B >= 1");
   const int64_t lda = rowstride(acts, 4 * H, "acts"), ldg = rowstride(dg_out, 4 * H, "dg_out");
   int64_t ldd = 0;
   if (dout && dout->defined()) { ldd = rowstride(*dout, H, "dout"); TORCH_CHECK(dout->size(0) == B, "dout batch"); }
   TORCH_CHECK(dg_out.size(0) == B && c_t.numel() == B * H && dc.numel() == B * H && dg16_out.numel() == B * 4 * H,
-              "lstm_peep_bwd_step: batch mismatch");
-  TORCH_CHECK(c_t.is_contiguous() && dc.is_contiguous() && dg16_out.is_contiguous(), "lstm_peep_bwd_step: contiguity");
+              "lstm_bwd_step: batch mismatch");
+  TORCH_CHECK(c_t.is_contiguous() && dc.is_contiguous() && dg16_out.is_contiguous(), "lstm_bwd_step: contiguity");
   if (dg16_next && dg16_next->defined()) TORCH_CHECK(dg16_next->numel() == B * 4 * H && dg16_next->is_contiguous(), "dg16_next");
   if (dh_ext && dh_ext->defined()) TORCH_CHECK(dh_ext->numel() == B * H && dh_ext->is_contiguous(), "dh_ext");
   if (c_prev && c_prev->defined()) TORCH_CHECK(c_prev->numel() == B * H && c_prev->is_contiguous(), "c_prev");
   const bool has_carry = carry && carry->defined();
   if (has_carry) TORCH_CHECK(carry->numel() == B * H && carry->is_contiguous(), "carry");
-  const PeepArgs a = peep_args("lstm_peep_bwd_step", pI, pF, pO, mask, order, B, H);
-  TORCH_CHECK(a.mask == nullptr || has_carry, "lstm_peep_bwd_step: a mask needs the carry buffer");
-  const int rc = bigdl_lstm_peep_bwd_step(cbf(WT16, "WT16"), ocbf(dg16_next, "dg16_next"), ocf(dout, "dout"), ldd,
-                                          ocf(dh_ext, "dh_ext"), cf(acts, "acts"), lda, ocf(c_prev, "c_prev"),
-                                          cf(c_t, "c_t"), mf(dc, "dc"), omf(carry, "carry"), mf(dg_out, "dg_out"), ldg,
-                                          mbf(dg16_out, "dg16_out"), a.pI, a.pF, a.pO, a.mask, a.g[0], a.g[1], a.g[2],
-                                          a.g[3], (int)B, (int)H, stream());
-  TORCH_CHECK(rc == 0, "lstm_peep_bwd_step: unsupported arguments");
+  const PeepArgs a = peep_args("lstm_bwd_step", pI, pF, pO, mask, order, B, H);
+  TORCH_CHECK(a.mask == nullptr || has_carry, "lstm_bwd_step: a mask needs the carry buffer");
+  const int rc = bigdl_lstm_bwd_step(cbf(WT16, "WT16"), ocbf(dg16_next, "dg16_next"), ocf(dout, "dout"), ldd,
+                                     ocf(dh_ext, "dh_ext"), cf(acts, "acts"), lda, ocf(c_prev, "c_prev"),
+                                     cf(c_t, "c_t"), mf(dc, "dc"), omf(carry, "carry"), mf(dg_out, "dg_out"), ldg,
+                                     mbf(dg16_out, "dg16_out"), a.pI, a.pF, a.pO, a.mask, a.g[0], a.g[1], a.g[2],
+                                     a.g[3], (int)B, (int)H, stream());
+  TORCH_CHECK(rc == 0, "lstm_bwd_step: unsupported arguments");
 }
 // Peephole weight gradients out [3, H] = (dp_i, dp_f, dp_o) from dg [B, T, 4H] (any batch / time strides, unit inner
 // stride), cs [T, B, H], c0 [B, H]; part = fp32 workspace of lstm_peep_wgrad_slices(T * B) * 3 * H elements.
@@ -1738,10 +1701,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("log_softmax_fwd", &log_softmax_fwd);
   m.def("log_softmax_bwd", &log_softmax_bwd);
   m.def("f32_to_bf16_rtz", &f32_to_bf16_rtz);
-  m.def("lstm_fwd_step", &lstm_fwd_step);
-  m.def("lstm_bwd_step", &lstm_bwd_step);
-  m.def("lstm_peep_fwd_step", &lstm_peep_fwd_step);
-  m.def("lstm_peep_bwd_step", &lstm_peep_bwd_step);
+  m.def("lstm_fwd_step", &lstm_fwd_step, py::arg("W16"), py::arg("h16_prev"), py::arg("xg"), py::arg("c_prev"),
+        py::arg("c_out"), py::arg("h_out"), py::arg("h16_out"), py::arg("acts"), py::arg("h_state") = py::none(),
+        py::arg("pI") = py::none(), py::arg("pF") = py::none(), py::arg("pO") = py::none(),
+        py::arg("mask") = py::none(), py::arg("order") = std::vector<int64_t>{0, 2, 1, 3});
+  m.def("lstm_bwd_step", &lstm_bwd_step, py::arg("WT16"), py::arg("dg16_next"), py::arg("dout"), py::arg("dh_ext"),
+        py::arg("acts"), py::arg("c_prev"), py::arg("c_t"), py::arg("dc"), py::arg("dg_out"), py::arg("dg16_out"),
+        py::arg("carry") = py::none(), py::arg("pI") = py::none(), py::arg("pF") = py::none(),
+        py::arg("pO") = py::none(), py::arg("mask") = py::none(), py::arg("order") = std::vector<int64_t>{0, 2, 1, 3});
   m.def("lstm_peep_wgrad_slices", &lstm_peep_wgrad_slices);
   m.def("lstm_peep_wgrad", &lstm_peep_wgrad);
   m.def("lstm_seq_supported", &lstm_seq_supported);

@@ -11,35 +11,13 @@
 //   backward S2  D = drz16_{t+1} . U_rz (N = H)  -> dh_t, then dn_pre_t / dz_pre_t (dx, bf16 GEMM operands)
 //            S1  D = dn16_t . U_n       (N = H)  -> d(r*h): dr_pre_t, and the r-path of dh_{t-1}
 // Tile = 16 batch rows x 16 output columns per workgroup, K split over up to 16 waves (each wave one or two
-// groups of 8 MFMA k-steps, see csrc/lstm.hip for why), partials reduced in LDS, then 256 threads run the
+// groups of 8 MFMA k-steps, see csrc/rnn_step.h for why), partials reduced in LDS, then 256 threads run the
 // epilogue coalesced along the output columns.
 #include "common.h"
 #include "kernels.h"
+#include "rnn_step.h"
 
 namespace {
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_f(float x) {
-  const float e = __expf(-2.f * fabsf(x));
-  const float t = (1.f - e) / (1.f + e);
-  return x < 0.f ? -t : t;
-}
-__device__ __forceinline__ v8s ld8(const bf16_t* p) { return *(const v8s*)p; }
-
-__device__ __forceinline__ v4f mfma_rows(const bf16_t* __restrict__ pa, const bf16_t* __restrict__ pb, int K, v4f acc) {
-  constexpr int CH = 8;
-  const int steps = K / 32, full = steps / CH * CH;
-  for (int s = 0; s < full; s += CH) {
-    v8s a[CH], b[CH];
-#pragma unroll
-    for (int i = 0; i < CH; ++i) { a[i] = ld8(pa + (s + i) * 32); b[i] = ld8(pb + (s + i) * 32); }
-#pragma unroll
-    for (int i = 0; i < CH; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[i], acc, 0, 0, 0);
-  }
-  for (int s = full; s < steps; ++s)
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(pa + s * 32), ld8(pb + s * 32), acc, 0, 0, 0);
-  return acc;
-}
 
 enum GruMode { FWD_RZ = 0, FWD_N = 1, BWD_H = 2, BWD_R = 3, BWD_H0 = 4 };
 
@@ -50,16 +28,17 @@ __device__ __forceinline__ void tile_gemm(const bf16_t* __restrict__ A, long lda
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, kh = lane >> 4;
   if (wave < KS) {
-    v4f acc = {0.f, 0.f, 0.f, 0.f};
+    v4f acc[1][1] = {{{0.f, 0.f, 0.f, 0.f}}};
     if (A != nullptr) {
       const int kl = K / KS;
       const int ba = b0 + r;
       // batch rows past B read row 0: an A row only feeds its own output row, which is never stored
-      acc = mfma_rows(A + (long)(ba < B ? ba : 0) * lda + (long)wave * kl + kh * 8,
-                      W + (long)(n0 + r) * K + (long)wave * kl + kh * 8, kl, acc);
+      const bf16_t* pa[1] = {A + (long)(ba < B ? ba : 0) * lda + (long)wave * kl + kh * 8};
+      const bf16_t* pw[1] = {W + (long)(n0 + r) * K + (long)wave * kl + kh * 8};
+      mfma_tiles<1, 1, false>(pw, pa, kl, acc);
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave][kh * 4 + i][r] = acc[i];   // D[row = batch][col = output]
+    for (int i = 0; i < 4; ++i) red[wave][kh * 4 + i][r] = acc[0][0][i];   // D[row = batch][col = output]
   }
   __syncthreads();
 }
@@ -144,14 +123,6 @@ __global__ void __launch_bounds__(1024) gru_step_kernel(GruArgs a) {
       break;
     }
   }
-}
-
-int ksplit(int K, int cap) {
-  int ks = K / 256;
-  if (ks < 1) ks = 1;
-  if (ks > cap) ks = cap;
-  while (ks > 1 && (K % (ks * 32)) != 0) --ks;
-  return ks;
 }
 
 }  // namespace

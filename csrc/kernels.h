@@ -349,29 +349,22 @@ void bigdl_log_softmax_fwd(const float* x, float* y, long rows, int cols, hipStr
 void bigdl_log_softmax_bwd(const float* y, const float* gy, float* gx, long rows, int cols, hipStream_t st);
 void bigdl_f32_to_bf16_rtz(const float* x, uint16_t* y, long n, hipStream_t st);
 
-// Fused LSTM steps (csrc/lstm.hip). W16 [4H][H] bf16 (gate blocks i, g, f, o), WT16 = W^T [H][4H] bf16.
-// Row strides: xg/h_out/acts/dout/dg_out rows are batch rows (ldx, ldh, lda, ldd, ldg elements apart).
+// Fused LSTM steps (csrc/lstm.hip) with optional peepholes, optional row mask and a caller-given gate layout. W16
+// [4H][H] bf16, WT16 = W^T [H][4H] bf16. Row strides: xg/h_out/acts/dout/dg_out rows are batch rows (ldx, ldh, lda,
+// ldd, ldg elements apart). gi, gf, gg, go: positions (a permutation of 0..3) of the i, f, g, o blocks in the [4H]
+// gate axis of xg / W16 / acts / dg; nn.LSTM's blocks i, g, f, o are (0, 2, 1, 3). pI, pF, pO fp32 [H], all three or
+// none. mask: this step's [B] bytes, 1 = valid row, or null. h_state (fp32 [B, H], in place, may be null) and carry
+// (fp32 [B, H], in place, required with a mask) hold what a masked row passes on. With nn.LSTM's layout and every
+// optional pointer null the specialised instantiation runs. Return -1 on an unsupported argument.
 int bigdl_lstm_fwd_step(const uint16_t* W16, const uint16_t* h16_prev, const float* xg, long ldx, const float* c_prev,
-                        float* c_out, float* h_out, long ldh, uint16_t* h16_out, float* acts, long lda, int B, int H,
-                        hipStream_t st);
+                        float* c_out, float* h_state, float* h_out, long ldh, uint16_t* h16_out, float* acts, long lda,
+                        const float* pI, const float* pF, const float* pO, const unsigned char* mask, int gi, int gf,
+                        int gg, int go, int B, int H, hipStream_t st);
 int bigdl_lstm_bwd_step(const uint16_t* WT16, const uint16_t* dg16_next, const float* dout, long ldd,
                         const float* dh_ext, const float* acts, long lda, const float* c_prev, const float* c_t,
-                        float* dc, float* dg_out, long ldg, uint16_t* dg16_out, int B, int H, hipStream_t st);
-// Fused LSTM steps with optional peepholes, optional row mask and a caller-given gate layout (csrc/lstm_peephole.hip).
-// gi, gf, gg, go: positions (a permutation of 0..3) of the i, f, g, o blocks in the [4H] gate axis of xg / W16 / acts /
-// dg. pI, pF, pO fp32 [H], all three or none. mask: this step's [B] bytes, 1 = valid row, or null. h_state (fp32
-// [B, H], in place, may be null) and carry (fp32 [B, H], in place, required with a mask) hold what a masked row
-// passes on. Return -1 on an unsupported argument.
-int bigdl_lstm_peep_fwd_step(const uint16_t* W16, const uint16_t* h16_prev, const float* xg, long ldx,
-                             const float* c_prev, float* c_out, float* h_state, float* h_out, long ldh,
-                             uint16_t* h16_out, float* acts, long lda, const float* pI, const float* pF,
-                             const float* pO, const unsigned char* mask, int gi, int gf, int gg, int go, int B, int H,
-                             hipStream_t st);
-int bigdl_lstm_peep_bwd_step(const uint16_t* WT16, const uint16_t* dg16_next, const float* dout, long ldd,
-                             const float* dh_ext, const float* acts, long lda, const float* c_prev, const float* c_t,
-                             float* dc, float* carry, float* dg_out, long ldg, uint16_t* dg16_out, const float* pI,
-                             const float* pF, const float* pO, const unsigned char* mask, int gi, int gf, int gg,
-                             int go, int B, int H, hipStream_t st);
+                        float* dc, float* carry, float* dg_out, long ldg, uint16_t* dg16_out, const float* pI,
+                        const float* pF, const float* pO, const unsigned char* mask, int gi, int gf, int gg, int go,
+                        int B, int H, hipStream_t st);
 // Peephole weight gradients out[3][H] = (dp_i, dp_f, dp_o) from the saved fp32 gate gradients dg (element (b, t, k) at
 // b * dg_sb + t * dg_st + k) and cell states cs [T, B, H] / c0 [B, H]; part is a [slices(T * B)][3][H] workspace.
 // Fixed summation order, no atomics.

@@ -8,7 +8,7 @@
 //   * lstm_drop_rep: x -> four masked bf16 copies [4][T*B][Kp] (time-major rows, optional ones column at k = K that
 //     carries the folded biases through the GEMM), the operand of ONE batched gate GEMM over the whole sequence;
 //     per step the same kernel masks h_{t-1} for the four recurrent GEMMs;
-//   * bmm_nt (bmm.hip) for the gate GEMMs, lstm_cell_fwd / bwd (lstm.hip) for the cell;
+//   * bmm_nt (bmm.hip) for the gate GEMMs, lstm_cell_fwd / bwd (elementwise.hip) for the cell;
 //   * lstm_drop_rep_bwd: the gradient of the four masked copies summed back through the masks (+ an optional
 //     addend, the step's output gradient), written in the input's [B][T][K] order;
 //   * lstm_pack_gate_w: gate-blocked bf16 weights [4][H][Kp] (+ the bias column) and their per-gate transposes.

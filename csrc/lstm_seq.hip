@@ -35,6 +35,7 @@
 // round after t = 0 produces dh0 = dg_0 W, so no transposed weight copy is ever made.
 #include "common.h"
 #include "kernels.h"
+#include "rnn_step.h"
 
 namespace {
 
@@ -82,13 +83,6 @@ unsigned* host_err_dev() {
     g_herr_dev = static_cast<unsigned*>(d);
   }
   return g_herr_dev;
-}
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_f(float x) {
-  const float e = __expf(-2.f * fabsf(x));
-  const float t = (1.f - e) / (1.f + e);
-  return x < 0.f ? -t : t;
 }
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, int bytes) {

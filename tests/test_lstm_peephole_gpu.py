@@ -1,5 +1,6 @@
-"""LSTMPeephole and maskZero LSTM sequences on the GPU: the fused step kernels of csrc/lstm_peephole.hip behind
-_LSTMPeepSeq against an fp64 loop of the same formulas, and the modules that route to them against the CPU engine."""
+"""LSTMPeephole and maskZero LSTM sequences on the GPU: the general instantiation of the fused step kernels of
+csrc/lstm.hip behind _LSTMPeepSeq against an fp64 loop of the same formulas, the modules that route to them against
+the CPU engine, and the general instantiation against the plain one."""
 import copy
 
 import pytest
@@ -294,3 +295,49 @@ def test_peephole_sequence_replays_from_a_hip_graph():
         torch.cuda.synchronize()
         for a, b in zip(res, eager_o + eager_g):
             assert torch.equal(a, b)
+
+
+def plain_and_general_step(C, B, H, seed=0):
+    """One forward and one backward step on the same finite random operands, once as the plain call (no optional
+    argument: the specialised instantiation) and once with zero peepholes, nn.LSTM's gate order, h_state and carry
+    given and no mask (the general instantiation doing the plain math). Returns the two lists of results
+    (c_out, h_out, h16_out, acts, dg_out, dg16_out, dc)."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    rnd = lambda *s: torch.randn(*s, device="cuda", generator=g)  # noqa: E731
+    W16 = (rnd(4 * H, H) / H ** 0.5).to(torch.bfloat16)
+    WT16 = W16.t().contiguous()
+    h16_prev, dg16_next = (rnd(B, H) * 0.5).to(torch.bfloat16), (rnd(B, 4 * H) * 0.1).to(torch.bfloat16)
+    xg, c_prev, dout, dh_ext, dc_in = rnd(B, 4 * H) * 0.5, rnd(B, H) * 0.5, rnd(B, H), rnd(B, H), rnd(B, H)
+    zero = torch.zeros(H, device="cuda")
+    f32 = lambda *s: torch.empty(*s, device="cuda")  # noqa: E731
+    runs = []
+    for general in (False, True):
+        opt = dict(pI=zero, pF=zero, pO=zero, order=ORDER_LSTM) if general else {}
+        fk = dict(h_state=torch.zeros(B, H, device="cuda"), **opt) if general else {}
+        bk = dict(carry=torch.zeros(B, H, device="cuda"), **opt) if general else {}
+        c_out, h_out, acts = f32(B, H), f32(B, H), f32(B, 4 * H)
+        h16_out = torch.empty(B, H, device="cuda", dtype=torch.bfloat16)
+        C.lstm_fwd_step(W16, h16_prev, xg, c_prev, c_out, h_out, h16_out, acts, **fk)
+        dc, dg_out = dc_in.clone(), f32(B, 4 * H)
+        dg16_out = torch.empty(B, 4 * H, device="cuda", dtype=torch.bfloat16)
+        C.lstm_bwd_step(WT16, dg16_next, dout, dh_ext, acts, c_prev, c_out, dc, dg_out, dg16_out, **bk)
+        runs.append([c_out, h_out, h16_out, acts, dg_out, dg16_out, dc])
+    torch.cuda.synchronize()
+    return runs
+
+
+@pytest.mark.parametrize("B,T,H", [(5, 2, 32), (37, 2, 64), (72, 2, 1024), (150, 2, 512), (130, 2, 1024)])
+def test_plain_and_general_instantiations_agree(B, T, H):
+    """(g) the two instantiations of the step kernels are one body: with zero peepholes, nn.LSTM's gate order and no
+    mask the general one gives the plain one's values exactly (torch.equal: a zero peephole term may turn -0 into +0
+    and nothing else). One step out of the middle of a T = 2 sequence: h16_prev and dg16_next are both there, and so
+    are dout and dh_ext. Shapes: KS < 4 with padded waves; a batch tail; NB = 2 in both directions (H = 1024, K split
+    16 in the backward); NB = 2 with 8 K chunks in both directions; NB = 2 with NU = 2 in the backward, which needs
+    4H / 16 >= 256 and more than 256 two-tile workgroups, so H = 1024 and B > 128."""
+    from bigdl_amd.ops import native
+
+    plain, general = plain_and_general_step(native.get(), B, H)
+    names = ["c_out", "h_out", "h16_out", "acts", "dg_out", "dg16_out", "dc"]
+    for n, a, b in zip(names, plain, general):
+        assert torch.isfinite(a.float()).all(), n
+        assert torch.equal(a, b), (n, (a.float() - b.float()).abs().max().item())

@@ -75,31 +75,32 @@ def main():
     print(f"fwd step fixed t       {timeit(lambda t=0: fwd(5)):7.2f} us")
     print(f"bwd step fixed t       {timeit(lambda t=0: bwd(5)):7.2f} us")
     if os.environ.get("PEEP", "0") != "0":
-        # csrc/lstm_peephole.hip next to the rows above: once with neither peepholes nor mask (the margin the general
-        # epilogue loses to the specialised kernel), once with both (every fourth row masked)
+        # the general instantiation of the same kernels next to the rows above: once doing the plain math (zero
+        # peepholes, nn.LSTM's gate order, h_state / carry given, no mask: what the flag saves the plain instantiation),
+        # once with peepholes and every fourth row masked
         peeps = [torch.randn(H, device=dev) * 0.1 for _ in range(3)]
+        zeros = [torch.zeros(H, device=dev)] * 3
         mask = (torch.arange(B, device=dev) % 4 != 3).to(torch.uint8)
         hst, carry = torch.zeros(B, H, device=dev), torch.zeros(B, H, device=dev)
 
         def pfwd(t=0, full=False):
             t = t % T
-            p = peeps if full else [None] * 3
-            C.lstm_peep_fwd_step(W16, h16[t & 1], xg[:, t], cs[t - 1] if t else None, cs[t], hst if full else None,
-                                 out[:, t], h16[(t + 1) & 1], acts[t], p[0], p[1], p[2], mask if full else None,
-                                 (0, 1, 2, 3) if full else (0, 2, 1, 3))
+            p = peeps if full else zeros
+            C.lstm_fwd_step(W16, h16[t & 1], xg[:, t], cs[t - 1] if t else None, cs[t], out[:, t], h16[(t + 1) & 1],
+                            acts[t], h_state=hst, pI=p[0], pF=p[1], pO=p[2], mask=mask if full else None,
+                            order=(0, 1, 2, 3) if full else (0, 2, 1, 3))
 
         def pbwd(t=0, full=False):
             t = t % T
-            p = peeps if full else [None] * 3
-            C.lstm_peep_bwd_step(WT16, dg16[(t + 1) & 1], dout[:, t], None, acts[t], cs[t - 1] if t else None, cs[t],
-                                 dc, carry if full else None, dxg[:, t], dg16[t & 1], p[0], p[1], p[2],
-                                 mask if full else None, (0, 1, 2, 3) if full else (0, 2, 1, 3))
+            p = peeps if full else zeros
+            C.lstm_bwd_step(WT16, dg16[(t + 1) & 1], dout[:, t], None, acts[t], cs[t - 1] if t else None, cs[t], dc,
+                            dxg[:, t], dg16[t & 1], carry=carry, pI=p[0], pF=p[1], pO=p[2],
+                            mask=mask if full else None, order=(0, 1, 2, 3) if full else (0, 2, 1, 3))
 
-        print(f"peep fwd step (plain)      {timeit(lambda t=0: pfwd(t)):7.2f} us")
-        print(f"peep bwd step (plain)      {timeit(lambda t=0: pbwd(t)):7.2f} us")
-        print(f"peep fwd step (peep+mask)  {timeit(lambda t=0: pfwd(t, True)):7.2f} us")
-        print(f"peep bwd step (peep+mask)  {timeit(lambda t=0: pbwd(t, True)):7.2f} us")
-
+        print(f"general fwd step (plain math)  {timeit(lambda t=0: pfwd(t)):7.2f} us")
+        print(f"general bwd step (plain math)  {timeit(lambda t=0: pbwd(t)):7.2f} us")
+        print(f"general fwd step (peep+mask)   {timeit(lambda t=0: pfwd(t, True)):7.2f} us")
+        print(f"general bwd step (peep+mask)   {timeit(lambda t=0: pbwd(t, True)):7.2f} us")
 
 if __name__ == "__main__":
     main()

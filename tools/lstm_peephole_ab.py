@@ -1,4 +1,4 @@
-"""A/B of the fused LSTMPeephole / maskZero LSTM sequence path (csrc/lstm_peephole.hip) against the Python time loop
+"""A/B of the fused LSTMPeephole / maskZero LSTM sequence path (csrc/lstm.hip) against the Python time loop
 (Cell.sequence): forward + backward of Recurrent(LSTMPeephole(1024, 1024)) and Recurrent(maskZero=True)(LSTM(1024,
 1024)) at B = 128, T = 64 in training mode, input lengths of the masked case spread over [T/2, T].
 
