@@ -270,6 +270,23 @@ bool conv_wgrad_uses_p8(std::vector<int64_t> geo, bool bias) {
   return bigdl_conv_wgrad_uses_p8(&a) != 0;
 }
 
+// What conv_wgrad would do with this geometry: [splits (-1 = stem pair kernel, 0 = atomic path, which splits by
+// itself), workspace floats, halo-kernel splits (0 = not the halo kernel), 1 if the 256 x 256 kernel takes it, 1 if
+// the register-staged conv_wgrad_kernel takes it]. Tests use it to check which kernel a case reaches.
+std::vector<int64_t> conv_wgrad_plan_info(std::vector<int64_t> geo, bool bias) {
+  TORCH_CHECK(geo.size() == 18, "conv_wgrad_plan_info: bad geometry");
+  WgradArgs a{};
+  int* f = &a.Nb;
+  for (int i = 0; i < 18; ++i) f[i] = (int)geo[i];
+  static float dummy;
+  a.dbias = bias ? &dummy : nullptr;
+  WgradArgs h = a, p = a;
+  const int halo = bigdl_wgrad_halo_plan(&h);
+  const int p8 = halo > 0 ? 0 : bigdl_conv_wgrad_uses_p8(&p);
+  const long wsn = bigdl_conv_wgrad_plan(&a);
+  return {a.splits, wsn, halo, p8, bigdl_conv_wgrad_uses_register_kernel(&a)};
+}
+
 void transpose_krsc(const Tensor& w, const Tensor& wt, int64_t K, int64_t RS, int64_t C) {
   TORCH_CHECK(w.numel() == K * RS * C && wt.numel() == K * RS * C, "transpose_krsc: size mismatch");
   bigdl_transpose_krsc(cbf(w, "w"), mbf(wt, "wt"), (int)K, (int)RS, (int)C, stream());
@@ -1759,9 +1776,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_conv_p8", &bigdl_set_conv_p8);
   m.def("set_wgrad_p8", &bigdl_set_wgrad_p8);
   m.def("conv_wgrad_uses_p8", &conv_wgrad_uses_p8);
+  m.def("conv_wgrad_plan_info", &conv_wgrad_plan_info);
   m.def("get_conv_g4", &bigdl_get_conv_g4);
   m.def("set_wgrad_g3", &bigdl_set_wgrad_g3);
   m.def("get_wgrad_g3", &bigdl_get_wgrad_g3);
+  m.def("set_wgrad_tr_asm", &bigdl_set_wgrad_tr_asm);
+  m.def("get_wgrad_tr_asm", &bigdl_get_wgrad_tr_asm);
   m.def("set_i8_g3", &bigdl_set_i8_g3);
   m.def("set_i8_p8", &bigdl_set_i8_p8);
   m.def("set_i8_s1", &bigdl_set_i8_s1);

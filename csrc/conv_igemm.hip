@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "conv_epilogue.h"
+#include "lds_tr.h"
 
 
 namespace {
@@ -857,11 +858,22 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs a) {
 // DMA instruction fills 4 consecutive rows x 16 granules; lane l writes slot l&15 of row 4j + (l>>4), so the
 // wswz row permutation f(row) is fixed per (lane, wave) and applied on the source side: the lane fetches
 // granule (l&15) ^ f. For the im2col operand that fixes each lane's (tap, channel) for the whole kernel.
+// Pipeline: two 64-pixel stages. An iteration issues the DMA of stage t + 1 (every lane issues all 8 instructions,
+// the zero granule for columns past Ncol / Kdim and rows past mend), computes stage t, and only then retires the
+// DMA (s_waitcnt vmcnt(0)) in front of the raw s_barrier that ends it: stage t was retired the same way one
+// iteration earlier, so nothing waits between the DMA issue and the fragment reads and the HBM round trip of stage
+// t + 1 runs under the 32 MFMAs of stage t.
+// TRASM = true reads the fragments with inline-assembly ds_read_b64_tr_b16 (lds_tr.h) behind a hand-placed
+// s_waitcnt lgkmcnt(0). TRASM = false (BIGDL_WGRAD_TR_ASM=0) reads them through the compiler intrinsic, in front of
+// which the compiler drains the DMA it has just issued (vmcnt(0)): the same results, without the overlap.
+// All LDS is one array (stages, then the pixel tables, then the bias scratch).
+template <bool TRASM>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_glds_kernel(WgradArgs a) {
   constexpr int STAGE = 2 * WBM * WT;
-  __shared__ __attribute__((aligned(1024))) bf16_t lds[2 * STAGE];
-  __shared__ int2 tbl[3][WBM];
-  __shared__ float red[4][128];
+  constexpr int TBLE = 3 * WBM * 4;           // pixel tables [3][WBM] of int2, in bf16 elements
+  __shared__ __attribute__((aligned(1024))) bf16_t lds[2 * STAGE + TBLE + 4 * 128 * 2];
+  int2* tbl = reinterpret_cast<int2*>(lds + 2 * STAGE);              // [3][WBM]
+  float* red = reinterpret_cast<float*>(lds + 2 * STAGE + TBLE);     // [4][128]
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -909,25 +921,31 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_glds_kernel(WgradArgs a) {
         e.x = 0;
         e.y = (int)0x80008000;
       }
-      tbl[slot][tid] = e;
+      tbl[slot * WBM + tid] = e;
     }
   };
+  // the zero granule's address, taken once (left to the compiler it is re-loaded through the GOT, with an
+  // lgkmcnt(0) wait, in front of every DMA of the loop)
+  const bf16_t* zg = g_zero_granule;
+  asm volatile("" : "+v"(zg));
   auto issue = [&](int mb, int tslot, int buf) {
     bf16_t* D = lds + buf * STAGE;
     bf16_t* X = D + WBM * WT;
+    int2 e[4];                                        // all table reads ahead of the first DMA
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e[i] = tbl[tslot * WBM + (i * 4 + wave) * 4 + Lg];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int rowblk = (i * 4 + wave) * 4;          // first of the 4 rows this instruction fills
-      const int row = rowblk + Lg;
-      const int m = mb + row;
-      const int2 e = tbl[tslot][row];
-      const int ih = (e.y >> 16) + rdh, iw = ((int)(short)(e.y & 0xffff)) + sdw;
-      // columns past Ncol / Kdim only feed discarded outputs: no DMA at all for those lanes
-      const bf16_t* pd = m < mend ? a.dy + (unsigned)(m * a.ldy + nn) : g_zero_granule;
-      const bool okx = (unsigned)ih < (unsigned)a.Hs && (unsigned)iw < (unsigned)a.Ws;
-      const bf16_t* px = okx ? a.src + (unsigned)((e.x + tapoff) * a.Cs + c) : g_zero_granule;
-      if (nvalid) glds16(pd, (LDS_PTR(void))(D + rowblk * WT));
-      if (kvalid) glds16(px, (LDS_PTR(void))(X + rowblk * WT));
+      const int m = mb + rowblk + Lg;
+      const int ih = (e[i].y >> 16) + rdh, iw = ((int)(short)(e[i].y & 0xffff)) + sdw;
+      // every lane issues every DMA (8 per wave and stage, exactly): columns past Ncol / Kdim, rows past mend and
+      // taps outside the image fetch the zero granule, so the issue has no exec-mask branches
+      const bf16_t* pd = (nvalid && m < mend) ? a.dy + (unsigned)(m * a.ldy + nn) : zg;
+      const bool okx = kvalid && (unsigned)ih < (unsigned)a.Hs && (unsigned)iw < (unsigned)a.Ws;
+      const bf16_t* px = okx ? a.src + (unsigned)((e[i].x + tapoff) * a.Cs + c) : zg;
+      glds16(pd, (LDS_PTR(void))(D + rowblk * WT));
+      glds16(px, (LDS_PTR(void))(X + rowblk * WT));
     }
   };
 
@@ -941,35 +959,72 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_glds_kernel(WgradArgs a) {
 
   const int G = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
 
+  // byte offsets of this lane's fragment rows 8G + q (lo) and 8G + q + 4 (hi) inside a [WBM][WT] operand image; the
+  // second 32-pixel half of a stage and the x image are immediate offsets (wswz's slot function repeats every 16 rows)
+  unsigned xlo[4], xhi[4], dlo[4], dhi[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    xlo[i] = 2u * wswz(8 * G + q, wk * 64 + i * 16 + 4 * p);
+    xhi[i] = 2u * wswz(8 * G + q + 4, wk * 64 + i * 16 + 4 * p);
+    dlo[i] = 2u * wswz(8 * G + q, wn * 64 + i * 16 + 4 * p);
+    dhi[i] = 2u * wswz(8 * G + q + 4, wn * 64 + i * 16 + 4 * p);
+  }
+  const unsigned lds0 = lds_byte_addr(lds);
+
   build_table(mbeg, 0);
   build_table(mbeg + WBM, 1);
   __syncthreads();
   issue(mbeg, 0, 0);
   build_table(mbeg + 2 * WBM, 2);
-  __syncthreads();
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
   int cur = 0, ts = 1;
   for (int mb = mbeg; mb < mend; mb += WBM) {
     const bool more = mb + WBM < mend;
+    // stage t + 1 into the other buffer: every wave left it behind at the barrier that ended the last iteration
     if (more) issue(mb + WBM, ts, cur ^ 1);
     const bf16_t* D = lds + cur * STAGE;
     const bf16_t* X = D + WBM * WT;
+    const unsigned sb = lds0 + cur * (STAGE * 2);
 #pragma unroll
     for (int ks = 0; ks < WBM / 32; ++ks) {
       v8s fx[4], fd[4];
-      const int rbase = ks * 32 + 8 * G + q;
+      if constexpr (TRASM) {
+        // stage t landed before the last barrier: no vmcnt wait here
+        v4s xl[4], xh[4], dl[4], dh[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int col = wk * 64 + i * 16 + 4 * p;
-        v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(X + wswz(rbase, col)));
-        v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(X + wswz(rbase + 4, col)));
-        fx[i] = v8s{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
+        for (int i = 0; i < 4; ++i) {
+          if (ks == 0) tr_pair2<WBM * WT * 2>(sb + xlo[i], sb + xhi[i], xl[i], xh[i]);
+          else tr_pair2<WBM * WT * 2 + 32 * WT * 2>(sb + xlo[i], sb + xhi[i], xl[i], xh[i]);
+        }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int col = wn * 64 + j * 16 + 4 * p;
-        v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(D + wswz(rbase, col)));
-        v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(D + wswz(rbase + 4, col)));
-        fd[j] = v8s{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        for (int j = 0; j < 4; ++j) {
+          if (ks == 0) tr_pair2<0>(sb + dlo[j], sb + dhi[j], dl[j], dh[j]);
+          else tr_pair2<32 * WT * 2>(sb + dlo[j], sb + dhi[j], dl[j], dh[j]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          fx[i] = tr_join(xl[i], xh[i]);
+          fd[i] = tr_join(dl[i], dh[i]);
+        }
+      } else {
+        const int rbase = ks * 32 + 8 * G + q;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int col = wk * 64 + i * 16 + 4 * p;
+          v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(X + wswz(rbase, col)));
+          v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(X + wswz(rbase + 4, col)));
+          fx[i] = tr_join(lo, hi);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int col = wn * 64 + j * 16 + 4 * p;
+          v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(D + wswz(rbase, col)));
+          v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(D + wswz(rbase + 4, col)));
+          fd[j] = tr_join(lo, hi);
+        }
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -985,9 +1040,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_glds_kernel(WgradArgs a) {
           }
       }
     }
-    // table of stage t+3 into the slot stage t used; then retire stage t+1's DMA (vmcnt(0)) before reuse
+    // table of stage t + 3 into the slot stage t used (read one iteration ago); then retire stage t + 1's DMA and
+    // this wave's table write, behind the MFMAs, before the barrier hands stage t's buffer back
     build_table(mb + 3 * WBM, (ts + 2) % 3);
-    __syncthreads();
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
     cur ^= 1;
     ts = ts == 2 ? 0 : ts + 1;
   }
@@ -1016,11 +1073,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_glds_kernel(WgradArgs a) {
     // row-group G; reduce the 4 groups through LDS
     if (do_bias) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) red[G][wn * 64 + j * 16 + (lane & 15)] = bsum[j];
+      for (int j = 0; j < 4; ++j) red[G * 128 + wn * 64 + j * 16 + (lane & 15)] = bsum[j];
     }
     __syncthreads();
     if (tid < 128) {
-      const float tot = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+      const float tot = red[tid] + red[128 + tid] + red[256 + tid] + red[384 + tid];
       const int n = n0 + tid;
       if (n < a.Ncol) atomicAdd(a.dbias + n, tot);
     }
@@ -1030,16 +1087,20 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_glds_kernel(WgradArgs a) {
 // Deep-pipelined variant of conv_wgrad_glds_kernel: 32-pixel LDS stages (16 KB: dy and x tiles of 32 x 128), THREE
 // stages with two in flight across every barrier (counted `s_waitcnt vmcnt`, raw s_barrier — the 2-stage kernel's
 // __syncthreads drains the DMA queue every 64 pixels), 3 workgroups per CU. Every lane issues every DMA (zero granule
-// for columns past Ncol / Kdim) so each wave's vmcnt counts L = 4 instructions per stage exactly. The pixel tables
-// and the bias reduction live behind the stages in the one __shared__ array.
+// for columns past Ncol / Kdim) so each wave's vmcnt counts L = 4 instructions per stage exactly. The counted waits
+// hold only with TRASM (fragment reads as inline assembly, lds_tr.h): in front of the intrinsic form of the read the
+// compiler drains the whole DMA queue. For the same reason the pixel tables are an LDS object of their own: a table
+// read or write inside the staging array may alias the DMA for the compiler, which then puts vmcnt(0) in front of
+// it. The bias reduction lives behind the stages (it runs after the loop).
+template <bool TRASM>
 __global__ __launch_bounds__(256, 3) void conv_wgrad_g3_kernel(WgradArgs a) {
   constexpr int PB = 32;                     // pixels per stage
   constexpr int STAGE = 2 * PB * WT;
   constexpr int NS = 3;
   constexpr int L = 2 * (PB / 16);           // DMA instructions per thread per stage (dy + x)
-  __shared__ __attribute__((aligned(1024))) bf16_t lds[NS * STAGE + (3 * PB * 8 + 4 * 128 * 4) / 2];
-  int2* tblv = reinterpret_cast<int2*>(lds + NS * STAGE);              // [3][PB]
-  float* red = reinterpret_cast<float*>(lds + NS * STAGE + 3 * PB * 4); // [4][128]
+  __shared__ __attribute__((aligned(1024))) bf16_t lds[NS * STAGE + 4 * 128 * 2];
+  __shared__ int2 tblv[3 * PB];
+  float* red = reinterpret_cast<float*>(lds + NS * STAGE);            // [4][128]
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1086,6 +1147,8 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_g3_kernel(WgradArgs a) {
       tblv[slot * PB + tid] = e;
     }
   };
+  const bf16_t* zg = g_zero_granule;     // taken once (see conv_wgrad_glds_kernel)
+  asm volatile("" : "+v"(zg));
   auto issue = [&](int mb, int slot, int buf) {
     bf16_t* D = lds + buf * STAGE;
     bf16_t* X = D + PB * WT;
@@ -1096,9 +1159,9 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_g3_kernel(WgradArgs a) {
       const int m = mb + row;
       const int2 e = tblv[slot * PB + row];
       const int ih = (e.y >> 16) + rdh, iw = ((int)(short)(e.y & 0xffff)) + sdw;
-      const bf16_t* pd = (nvalid && m < mend) ? a.dy + (unsigned)(m * a.ldy + nn) : g_zero_granule;
+      const bf16_t* pd = (nvalid && m < mend) ? a.dy + (unsigned)(m * a.ldy + nn) : zg;
       const bool okx = kvalid && (unsigned)ih < (unsigned)a.Hs && (unsigned)iw < (unsigned)a.Ws;
-      const bf16_t* px = okx ? a.src + (unsigned)((e.x + tapoff) * a.Cs + c) : g_zero_granule;
+      const bf16_t* px = okx ? a.src + (unsigned)((e.x + tapoff) * a.Cs + c) : zg;
       glds16(pd, (LDS_PTR(void))(D + rowblk * WT));
       glds16(px, (LDS_PTR(void))(X + rowblk * WT));
     }
@@ -1113,6 +1176,15 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_g3_kernel(WgradArgs a) {
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};
   const int G = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
   const int nst = (mend - mbeg + PB - 1) / PB;
+  unsigned xlo[4], xhi[4], dlo[4], dhi[4];   // fragment row byte offsets, as in conv_wgrad_glds_kernel
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    xlo[i] = 2u * wswz(8 * G + q, wk * 64 + i * 16 + 4 * p);
+    xhi[i] = 2u * wswz(8 * G + q + 4, wk * 64 + i * 16 + 4 * p);
+    dlo[i] = 2u * wswz(8 * G + q, wn * 64 + i * 16 + 4 * p);
+    dhi[i] = 2u * wswz(8 * G + q + 4, wn * 64 + i * 16 + 4 * p);
+  }
+  const unsigned lds0 = lds_byte_addr(lds);
 
   build_table(mbeg, 0);
   build_table(mbeg + PB, 1);
@@ -1136,20 +1208,36 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_g3_kernel(WgradArgs a) {
     const bf16_t* X = D + PB * WT;
     {
       v8s fx[4], fd[4];
-      const int rbase = 8 * G + q;
+      if constexpr (TRASM) {
+        const unsigned sb = lds0 + cur * (STAGE * 2);
+        v4s xl[4], xh[4], dl[4], dh[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int col = wk * 64 + i * 16 + 4 * p;
-        v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(X + wswz(rbase, col)));
-        v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(X + wswz(rbase + 4, col)));
-        fx[i] = v8s{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
+        for (int i = 0; i < 4; ++i) tr_pair2<PB * WT * 2>(sb + xlo[i], sb + xhi[i], xl[i], xh[i]);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int col = wn * 64 + j * 16 + 4 * p;
-        v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(D + wswz(rbase, col)));
-        v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(D + wswz(rbase + 4, col)));
-        fd[j] = v8s{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        for (int j = 0; j < 4; ++j) tr_pair2<0>(sb + dlo[j], sb + dhi[j], dl[j], dh[j]);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          fx[i] = tr_join(xl[i], xh[i]);
+          fd[i] = tr_join(dl[i], dh[i]);
+        }
+      } else {
+        const int rbase = 8 * G + q;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int col = wk * 64 + i * 16 + 4 * p;
+          v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(X + wswz(rbase, col)));
+          v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(X + wswz(rbase + 4, col)));
+          fx[i] = tr_join(lo, hi);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int col = wn * 64 + j * 16 + 4 * p;
+          v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(D + wswz(rbase, col)));
+          v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(v4s))(D + wswz(rbase + 4, col)));
+          fd[j] = tr_join(lo, hi);
+        }
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -1255,7 +1343,10 @@ typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 
 // DIRECT: 1 x 1, stride 1, no padding (GEMM-shaped): x row = output pixel, no per-row geometry in the DMA issue
 // (the general path divides every DMA row's pixel index into (image, oh, ow): ~9 VALU instructions per MFMA)
-template <bool DIRECT>
+// TRASM: the transposing fragment reads as inline assembly (lds_tr.h). Through the intrinsic (TRASM = false,
+// BIGDL_WGRAD_TR_ASM=0) the compiler puts s_waitcnt vmcnt(0) in front of every group of reads, behind the DMA issue
+// of the same phase, and the counted waits below never get to count.
+template <bool DIRECT, bool TRASM>
 __global__ __launch_bounds__(512, 2) void conv_wgrad_p8_kernel(WgradArgs a) {
   constexpr int PIX = 64;                          // pixels per K-step
   constexpr int PC = 128;                          // columns per piece
@@ -1305,6 +1396,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_p8_kernel(WgradArgs a) {
   }
   const int ohw = a.OH * a.OW;
 
+  const bf16_t* zg = g_zero_granule;     // taken once: left to the compiler it is re-loaded through the GOT per issue
+  asm volatile("" : "+v"(zg));
   // piece P (0 x q0, 1 dy q0, 2 x q1, 3 dy q1) of K-step kt into buffer buf: 2 DMA instructions per thread
   auto issue = [&](int kt, int buf, int P) {
     bf16_t* base = lds + buf * BUF + P * PIECE;
@@ -1313,7 +1406,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_p8_kernel(WgradArgs a) {
     for (int j = 0; j < 2; ++j) {
       const int row = (j * 8 + wave) * 4 + (lane >> 4);
       const int m = mbeg + kt * PIX + row;
-      const bf16_t* src = g_zero_granule;
+      const bf16_t* src = zg;
       if (m < mend) {
         if ((P & 1) == 0) {
           if (DIRECT) {
@@ -1349,7 +1442,23 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_p8_kernel(WgradArgs a) {
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
-  v8s fa[4][2], fb[4][2];
+  // fragments as two 8-byte halves [.., K-half, lo / hi]: an inline-assembly read fills a half, and the halves are
+  // joined only behind the s_waitcnt lgkmcnt(0) of compute(). p8w_f is the same for rows r, r + 4 and r + 32, so the
+  // second row and the K-half are immediate offsets (1024 and 8192 bytes) from the lane's byte offset of row 8 G + q'
+  v4s fa[4][2][2], fb[4][2][2];
+  auto tr_off = [&](int c0) -> unsigned {
+    const int row = 8 * G + qq, col = c0 + 4 * pp;
+    return (unsigned)(row * PC + (((col >> 3) ^ p8w_f(row)) << 3) + (col & 7)) * 2u;
+  };
+  unsigned atr[4], btr[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) atr[i] = tr_off(wm * 64 + i * 16);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) btr[j] = tr_off(wn * 32 + j * 16);
+  auto halves = [&](const v8s v, v4s* d) {
+    d[0] = v4s{v[0], v[1], v[2], v[3]};
+    d[1] = v4s{v[4], v[5], v[6], v[7]};
+  };
   auto quad = [&](int ib, int jb) {
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh)
@@ -1357,20 +1466,33 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_p8_kernel(WgradArgs a) {
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[ib + i][jb + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][kh], fb[jb + j][kh], acc[ib + i][jb + j], 0, 0, 0);
+          acc[ib + i][jb + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              tr_join(fa[i][kh][0], fa[i][kh][1]), tr_join(fb[jb + j][kh][0], fb[jb + j][kh][1]), acc[ib + i][jb + j], 0, 0, 0);
   };
   auto read_a = [&](const bf16_t* P) {            // x: this wave's kk quadrant = piece columns wm * 64 + 16 i
+    const unsigned pa = lds_byte_addr(P);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      fa[i][0] = frag(P, 0, wm * 64 + i * 16);
-      fa[i][1] = frag(P, 1, wm * 64 + i * 16);
+      if constexpr (TRASM) {
+        tr_pair<0>(pa + atr[i], fa[i][0][0], fa[i][0][1]);
+        tr_pair<8192>(pa + atr[i], fa[i][1][0], fa[i][1][1]);
+      } else {
+        halves(frag(P, 0, wm * 64 + i * 16), fa[i][0]);
+        halves(frag(P, 1, wm * 64 + i * 16), fa[i][1]);
+      }
     }
   };
   auto read_b = [&](const bf16_t* P, int jb) {    // dy: this wave's n quadrant = piece columns wn * 32 + 16 j
+    const unsigned pb = lds_byte_addr(P);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      fb[jb + j][0] = frag(P, 0, wn * 32 + j * 16);
-      fb[jb + j][1] = frag(P, 1, wn * 32 + j * 16);
+      if constexpr (TRASM) {
+        tr_pair<0>(pb + btr[j], fb[jb + j][0][0], fb[jb + j][0][1]);
+        tr_pair<8192>(pb + btr[j], fb[jb + j][1][0], fb[jb + j][1][1]);
+      } else {
+        halves(frag(P, 0, wn * 32 + j * 16), fb[jb + j][0]);
+        halves(frag(P, 1, wn * 32 + j * 16), fb[jb + j][1]);
+      }
     }
   };
   // bias gradient: the kk-tile-0 workgroups also sum their dy fragments over the pixels, wave half wm taking the
@@ -1383,7 +1505,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_p8_kernel(WgradArgs a) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int kh = 0; kh < 2; ++kh) {
-        const v8bf f = __builtin_bit_cast(v8bf, fb[jb + j][kh]);
+        const v8bf f = __builtin_bit_cast(v8bf, tr_join(fb[jb + j][kh][0], fb[jb + j][kh][1]));
 #pragma unroll
         for (int e = 0; e < 4; ++e) bsum[j] = __builtin_amdgcn_fdot2_f32_bf16(v2bf{f[2 * e], f[2 * e + 1]}, one, bsum[j], false);
       }
@@ -3134,6 +3256,29 @@ static bool wgrad_g3() {
 void bigdl_set_wgrad_g3(int v) { g_wgrad_g3 = v; }
 int bigdl_get_wgrad_g3() { return wgrad_g3() ? 1 : 0; }
 
+int g_wgrad_tr_asm = -1;
+// BIGDL_WGRAD_TR_ASM: 1 (default) = the weight-gradient kernels read their fragments with inline-assembly
+// transposing reads and hand-placed waits (lds_tr.h); 0 = through the compiler intrinsic, which drains the LDS-DMA
+// in front of every group of reads. Same kernels (a template flag), same results bit for bit; for A/B runs.
+static bool wgrad_tr_asm() {
+  if (g_wgrad_tr_asm < 0) {
+    const char* e = getenv("BIGDL_WGRAD_TR_ASM");
+    g_wgrad_tr_asm = e ? atoi(e) : 1;
+  }
+  return g_wgrad_tr_asm != 0;
+}
+void bigdl_set_wgrad_tr_asm(int v) { g_wgrad_tr_asm = v; }
+int bigdl_get_wgrad_tr_asm() { return wgrad_tr_asm() ? 1 : 0; }
+
+static void launch_wgrad_g3(const WgradArgs& a, int blocks, hipStream_t st) {
+  if (wgrad_tr_asm()) conv_wgrad_g3_kernel<true><<<dim3(blocks), dim3(256), 0, st>>>(a);
+  else conv_wgrad_g3_kernel<false><<<dim3(blocks), dim3(256), 0, st>>>(a);
+}
+static void launch_wgrad_glds(const WgradArgs& a, int blocks, hipStream_t st) {
+  if (wgrad_tr_asm()) conv_wgrad_glds_kernel<true><<<dim3(blocks), dim3(256), 0, st>>>(a);
+  else conv_wgrad_glds_kernel<false><<<dim3(blocks), dim3(256), 0, st>>>(a);
+}
+
 // BIGDL_WGRAD_P8: 1 (default) = conv_wgrad_p8_kernel where it measured faster (below), 2 = on every layer with
 // Ncol >= 256 and Kdim >= 256 (tests / A/B), 0 = off.
 // Returns its pixel split (>= 1) or 0 when it does not apply; sets m_per_split.
@@ -3176,6 +3321,12 @@ static int p8w_pick(WgradArgs* a) {
 int bigdl_conv_wgrad_uses_p8(const WgradArgs* a_in) {
   WgradArgs a = *a_in;
   return p8w_pick(&a) > 0 ? 1 : 0;
+}
+
+// 1 when a weight gradient that is left to the 128 x 128 kernels runs the register-staged conv_wgrad_kernel
+// (no LDS-DMA build, or the half-empty-tile rule) instead of conv_wgrad_glds_kernel
+int bigdl_conv_wgrad_uses_register_kernel(const WgradArgs* a) {
+  return (conv_impl() < 1 || wgrad_prefers_atomic(a)) ? 1 : 0;
 }
 
 long bigdl_conv_wgrad_plan(WgradArgs* a) {
@@ -3269,8 +3420,14 @@ static int conv_wgrad_impl(const WgradArgs* a_in, hipStream_t st) {
       const int tiles = ((a.Ncol + 255) / 256) * ((a.Kdim + 255) / 256);
       const bool direct = a.R == 1 && a.S == 1 && a.sh == 1 && a.sw == 1 && a.ph == 0 && a.pw == 0 && a.Hs == a.OH &&
                           a.Ws == a.OW;
-      if (direct) conv_wgrad_p8_kernel<true><<<dim3(tiles, p8w), dim3(512), 0, st>>>(b);
-      else conv_wgrad_p8_kernel<false><<<dim3(tiles, p8w), dim3(512), 0, st>>>(b);
+      const dim3 grid(tiles, p8w);
+      if (wgrad_tr_asm()) {
+        if (direct) conv_wgrad_p8_kernel<true, true><<<grid, dim3(512), 0, st>>>(b);
+        else conv_wgrad_p8_kernel<false, true><<<grid, dim3(512), 0, st>>>(b);
+      } else {
+        if (direct) conv_wgrad_p8_kernel<true, false><<<grid, dim3(512), 0, st>>>(b);
+        else conv_wgrad_p8_kernel<false, false><<<grid, dim3(512), 0, st>>>(b);
+      }
       if (p8w > 1) {
         const long n4 = (long)a.Ncol * a.Kdim / 4;
         const int blocks = (int)std::min<long>((n4 + 255) / 256, 8192);
@@ -3284,8 +3441,8 @@ static int conv_wgrad_impl(const WgradArgs* a_in, hipStream_t st) {
   if (a.ws != nullptr && a.splits > 1 && conv_impl() >= 1) {
     const int tiles = ((a.Ncol + WT - 1) / WT) * ((a.Kdim + WT - 1) / WT);
     const int spad = (a.splits + 7) / 8 * 8;
-    if (wgrad_g3()) conv_wgrad_g3_kernel<<<dim3(tiles * spad), dim3(256), 0, st>>>(a);
-    else conv_wgrad_glds_kernel<<<dim3(tiles * spad), dim3(256), 0, st>>>(a);
+    if (wgrad_g3()) launch_wgrad_g3(a, tiles * spad, st);
+    else launch_wgrad_glds(a, tiles * spad, st);
     const long n4 = (long)a.Ncol * a.Kdim / 4;
     const int blocks = (int)std::min<long>((n4 + 255) / 256, 8192);
     // ~2048 reduce workgroups in total, >= 4 splits per group, <= 64-way atomic contention
@@ -3315,9 +3472,9 @@ static int conv_wgrad_impl(const WgradArgs* a_in, hipStream_t st) {
   a.m_per_split = mps;
   a.splits = splits;
   if (conv_impl() >= 1 && !wgrad_prefers_atomic(&a) && wgrad_g3())
-    conv_wgrad_g3_kernel<<<dim3(tiles * ((splits + 7) / 8 * 8)), dim3(256), 0, st>>>(a);
+    launch_wgrad_g3(a, tiles * ((splits + 7) / 8 * 8), st);
   else if (conv_impl() >= 1 && !wgrad_prefers_atomic(&a))
-    conv_wgrad_glds_kernel<<<dim3(tiles * ((splits + 7) / 8 * 8)), dim3(256), 0, st>>>(a);
+    launch_wgrad_glds(a, tiles * ((splits + 7) / 8 * 8), st);
   else conv_wgrad_kernel<<<dim3(tiles, splits), dim3(256), 0, st>>>(a);
   HIP_LAUNCH_CHECK();
   return 0;

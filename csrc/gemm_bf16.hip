@@ -31,6 +31,7 @@
 // fragments against a ones operand, by the workgroups of tile column 0 alone (slices combined in slice order).
 #include "common.h"
 #include "kernels.h"
+#include "lds_tr.h"     // tr_pair: the transposing reads as inline assembly (no compiler-inserted DMA drain)
 
 namespace {
 
@@ -38,16 +39,6 @@ constexpr int GB_SLOT = 256 * 256 + 256;   // floats per (tile, slice) slot: acc
 constexpr int GB_CUS = 256;
 
 __device__ __forceinline__ int gb_f(int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); }
-
-// Two transposing reads (rows r and r + 4 of one fragment) as inline assembly: the compiler's wait-count pass does
-// not know which LDS bytes the intrinsic form reads and drains every LDS-DMA in flight (vmcnt(0)) before it, which
-// serialises the pipeline. The results are pending until the caller's own s_waitcnt lgkmcnt(0).
-template <int OFF>
-__device__ __forceinline__ void tr_pair(unsigned addr, v4s& lo, v4s& hi) {
-  asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"
-               : "=&v"(lo), "=&v"(hi)
-               : "v"(addr), "n"(OFF), "n"(OFF + 1024));
-}
 
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, unsigned off, LDS_PTR(void) l) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, l, 16, off, 0, 0, 0);

@@ -297,6 +297,9 @@ int bigdl_conv_wgrad_uses_p8(const WgradArgs* a);
 int bigdl_get_conv_g4();
 void bigdl_set_wgrad_g3(int v);
 int bigdl_get_wgrad_g3();
+int bigdl_conv_wgrad_uses_register_kernel(const WgradArgs* a);
+void bigdl_set_wgrad_tr_asm(int v);
+int bigdl_get_wgrad_tr_asm();
 void bigdl_set_i8_g3(int v);
 void bigdl_set_i8_p8(int v);
 void bigdl_set_i8_epi(int v);
