@@ -15,7 +15,10 @@ disables dropout.
 
 MI355X execution: projections are GEMMs over all B*L rows; the attention core (ops.attention) dispatches to the
 fused flash-attention HIP kernel on the GPU engine (online softmax in registers, no [L, L] score tensor in
-HBM, causal block skipping) and to the explicit math path elsewhere.
+HBM, causal block skipping) and to the explicit math path elsewhere. Beam-search prediction of a Translation
+Transformer decodes incrementally on a per-call _DecodeState (preallocated KV caches, csrc/attn_decode.hip) when native
+decoding is on (BIGDL_DECODE_NATIVE / bigdl.decode.native; the GPU engine's default), else through the reference's
+cache Tables.
 """
 import math
 
@@ -25,6 +28,7 @@ import torch.nn.functional as F
 from ..ops.conv_fn import linear as _linear
 
 from ..ops.attention import attention as attention_core
+from ..ops.attention import decode_attention, decode_cache_dtype, decode_native, kv_append, kv_reorder
 from ..utils.table import Table
 from .abstractnn import AbstractModule, TensorModule
 from .activation import MulConstant, ReLU
@@ -451,6 +455,83 @@ def _copy_state(dst, src):
     _copy_module_state(dst, src)
 
 
+class _DecodeState:
+    """Incremental decoding state of one beam-search call over a Translation Transformer: preallocated
+    self-attention caches [layers][2][B * beam][maxDecodeLength][hidden] in two ping-pong copies, the encoder K / V
+    [layers][2][B][Ls][hidden] projected once per sentence, the padding bias [B, Ls] and rows = n // beam, through
+    which every beam reads its sentence's encoder K / V. bf16 on the GPU engine (ops.attention decode kernels), fp32
+    on the CPU engine and for head dims the kernels do not cover (the torch math of the same signatures). Lives for
+    one SequenceBeamSearch.updateOutput and is never stored on a module. Decoder modules are found by the names
+    ``Transformer.block`` gives them."""
+
+    def __init__(self, tr, enc, att_bias, beam, maxDecodeLength):
+        assert not tr.train, "incremental decoding runs in evaluate mode"
+        self.tr = tr
+        B, Ls, hidden = enc.shape
+        dev = enc.device
+        self.N, self.heads, self.hidden = B * beam, tr.numHeads, hidden
+        self.scale = (hidden // tr.numHeads) ** -0.5
+        dt = decode_cache_dtype(enc.is_cuda, hidden, tr.numHeads)
+        stack, L = tr.decoderStack, tr.numHiddenlayers
+        self.layers = []
+        for i in range(L):
+            sa, ed, ff = f"decoder_self_attention_{i}/", f"decoder_encdec_attention_{i}/", f"decoder_ffn_{i}/"
+            mods = [stack[sa + "norm"], stack[sa + "self_attention"], stack[ed + "norm"],
+                    stack[ed + "encdec_attention"], stack[ff + "norm"], stack[ff + "ffn"]]
+            assert all(m is not None for m in mods), f"decoder layer {i}: modules not found by name"
+            self.layers.append(mods)
+        final = [m for m in stack.findModules("LayerNormalization")
+                 if not any(m is mods[j] for mods in self.layers for j in (0, 2, 4))]
+        assert len(final) == 1, "decoder stack: expected one output LayerNormalization"
+        self.final_norm = final[0]
+        # positions at or past the decoded length are never read (attn_decode, kv_reorder), so nothing is cleared
+        self.cache = [torch.empty(L, 2, self.N, maxDecodeLength, hidden, dtype=dt, device=dev) for _ in range(2)]
+        self.cur, self.length = 0, 0
+        with torch.no_grad():
+            encf = enc.detach().float()
+            self.enc_kv = torch.empty(L, 2, B, Ls, hidden, dtype=dt, device=dev)
+            for i, mods in enumerate(self.layers):
+                self.enc_kv[i, 0] = _linear(encf, mods[3].keyLayer.weight)
+                self.enc_kv[i, 1] = _linear(encf, mods[3].valueLayer.weight)
+        self.bias = att_bias.detach().float().reshape(B, Ls).contiguous()
+        self.rows = (torch.arange(self.N, device=dev) // beam).to(torch.int32)
+        self.base = (torch.arange(B, device=dev) * beam).view(B, 1)
+        self.timing = TransformerOperation.getPositionEncode(maxDecodeLength + 1, hidden, device=dev)
+        tr._share()
+
+    def _attend(self, att, x, kc, vc, length, rows=None, bias=None):
+        q = _linear(x, att.queryLayer.weight).view(self.N, self.hidden) * self.scale
+        o = decode_attention(q, kc, vc, length, self.heads, rows, bias)
+        return _linear(o.view(self.N, 1, self.hidden), att.outputLayer.weight)
+
+    @torch.no_grad()
+    def step(self, ids, i):
+        """ids [B * beam, >= i + 1] (1-based, 0 = padding): logits [B * beam, vocab] of position i."""
+        tr, N, hidden = self.tr, self.N, self.hidden
+        x = tr.embeddingLayer.forward(ids[:, i:i + 1]).float() + self.timing[i]
+        cache = self.cache[self.cur]
+        for li, (sa_norm, sa, ed_norm, ed, ffn_norm, ffn) in enumerate(self.layers):
+            y = sa_norm.forward(x)
+            k = _linear(y, sa.keyLayer.weight).view(N, hidden)
+            v = _linear(y, sa.valueLayer.weight).view(N, hidden)
+            kv_append(k, v, cache[li, 0], cache[li, 1], i)
+            x = x + self._attend(sa, y, cache[li, 0], cache[li, 1], i + 1)
+            y = ed_norm.forward(x)
+            x = x + self._attend(ed, y, self.enc_kv[li, 0], self.enc_kv[li, 1], self.enc_kv.shape[3], self.rows,
+                                 self.bias)
+            x = x + ffn.forward(ffn_norm.forward(x))
+        self.length = i + 1
+        out = self.final_norm.forward(x)
+        return tr.linearSharedWeigths.forward(out).squeeze(1)
+
+    @torch.no_grad()
+    def reorder(self, parent):
+        """parent [B, beam]: beam b of every sentence continues from its beam parent[:, b]."""
+        flat = (self.base + parent).reshape(-1).to(torch.int32)
+        kv_reorder(self.cache[self.cur], self.cache[1 - self.cur], flat, self.length)
+        self.cur = 1 - self.cur
+
+
 # ---------------------------------------------------------------------------------------------- beam search
 class SequenceBeamSearch(AbstractModule):
     """Beam search over ``symbolToLogits`` (S/nn/SequenceBeamSearch.scala:39). Input T(encoder_outputs,
@@ -492,32 +573,40 @@ class SequenceBeamSearch(AbstractModule):
         alive_seq = torch.full((B, K, 1), float(self.paddingValue), device=dev)
         alive_lp = torch.full((B, K), self.INF, device=dev)
         alive_lp[:, 0] = 0.0
-        alive_enc = enc.unsqueeze(1).expand(B, K, *enc.shape[1:]).contiguous()
-        alive_bias = att_bias.unsqueeze(1).expand(B, K, *att_bias.shape[1:]).contiguous()
-        layers = {f"layer_{j}_{c}": None for j in range(1, self.numHiddenLayers + 1) for c in "kv"}
+        # native incremental decoding (_DecodeState): the owning Transformer's own logit function only; the state
+        # keeps the caches and the per-sentence encoder K / V, so nothing of them is expanded or gathered here
+        state = self._native_state(enc, att_bias)
+        if state is None:
+            alive_enc = enc.unsqueeze(1).expand(B, K, *enc.shape[1:]).contiguous()
+            alive_bias = att_bias.unsqueeze(1).expand(B, K, *att_bias.shape[1:]).contiguous()
+            layers = {f"layer_{j}_{c}": None for j in range(1, self.numHiddenLayers + 1) for c in "kv"}
         fin_seq = torch.zeros_like(alive_seq)
         fin_scores = torch.full((B, K), self.INF, device=dev)
         fin_flags = torch.zeros(B, K, dtype=torch.bool, device=dev)
         i = 0
         while self._continue(i, alive_lp, fin_scores, fin_flags):
             flat = lambda t: t.reshape(B * K, *t.shape[2:])  # noqa: E731
-            cache = Table()
-            for name, t in layers.items():
-                cache[name] = flat(t) if t is not None else torch.zeros(0, device=dev)
-            logits, new_cache = self.symbolToLogits(flat(alive_seq), i, self.maxDecodeLength, flat(alive_enc),
-                                                    flat(alive_bias), cache)
+            if state is not None:
+                logits = state.step(flat(alive_seq), i)
+            else:
+                cache = Table()
+                for name, t in layers.items():
+                    cache[name] = flat(t) if t is not None else torch.zeros(0, device=dev)
+                logits, new_cache = self.symbolToLogits(flat(alive_seq), i, self.maxDecodeLength, flat(alive_enc),
+                                                        flat(alive_bias), cache)
             logits = logits.reshape(B, K, V).float()
             lp = torch.log_softmax(logits, -1) + alive_lp.unsqueeze(2)
             top_lp, top_ix = torch.topk(lp.reshape(B, K * V), 2 * K, dim=-1)
             beam_ix = top_ix // V
             top_seq = self._gather(alive_seq, beam_ix)
-            top_enc = self._gather(alive_enc, beam_ix)
-            top_bias = self._gather(alive_bias, beam_ix)
-            top_layers = {}
-            for name in layers:
-                t = new_cache[name]
-                top_layers[name] = self._gather(t.reshape(B, K, *t.shape[1:]), beam_ix) if t is not None and \
-                    t.numel() else None
+            if state is None:
+                top_enc = self._gather(alive_enc, beam_ix)
+                top_bias = self._gather(alive_bias, beam_ix)
+                top_layers = {}
+                for name in layers:
+                    t = new_cache[name]
+                    top_layers[name] = self._gather(t.reshape(B, K, *t.shape[1:]), beam_ix) if t is not None and \
+                        t.numel() else None
             ids = (top_ix % V + 1).float().unsqueeze(2)
             new_seq = torch.cat([top_seq, ids], 2)
             new_fin = new_seq[:, :, -1] == self.eosID
@@ -526,9 +615,12 @@ class SequenceBeamSearch(AbstractModule):
             _, ix = torch.topk(lp_alive, K, dim=-1)
             alive_seq = self._gather(new_seq, ix)
             alive_lp = torch.gather(lp_alive, 1, ix)
-            alive_enc = self._gather(top_enc, ix)
-            alive_bias = self._gather(top_bias, ix)
-            layers = {n: (self._gather(t, ix) if t is not None else None) for n, t in top_layers.items()}
+            if state is None:
+                alive_enc = self._gather(top_enc, ix)
+                alive_bias = self._gather(top_bias, ix)
+                layers = {n: (self._gather(t, ix) if t is not None else None) for n, t in top_layers.items()}
+            elif i + 1 < self.maxDecodeLength:
+                state.reorder(beam_ix.gather(1, ix))     # the top-2K and alive-K gathers composed: one parent index
             # finished set
             fin_seq = torch.cat([fin_seq, torch.full((B, K, 1), float(self.paddingValue), device=dev)], 2)
             new_scores = top_lp / self._lnorm(i + 1) + (~new_fin).float() * self.INF
@@ -544,6 +636,17 @@ class SequenceBeamSearch(AbstractModule):
         seq = torch.where(any_fin.view(B, 1, 1), fin_seq, alive_seq)
         scores = torch.where(any_fin.view(B, 1), fin_scores, alive_lp)
         return Table(seq, scores)
+
+    def _native_state(self, enc, att_bias):
+        """A _DecodeState when the logit function is a Translation Transformer's own ``symbols`` and native
+        decoding is on (BIGDL_DECODE_NATIVE / bigdl.decode.native), else None: the Table path."""
+        fn = self.symbolToLogits
+        owner = getattr(fn, "__self__", None)
+        if not isinstance(owner, Transformer) or getattr(fn, "__func__", None) is not Transformer.symbols:
+            return None
+        if owner.decoderStack is None or owner.train or not decode_native(enc.is_cuda):
+            return None
+        return _DecodeState(owner, enc, att_bias, self.beamSize, self.maxDecodeLength)
 
     def _continue(self, i, alive_lp, fin_scores, fin_flags):
         if i >= self.maxDecodeLength:

@@ -167,6 +167,10 @@ class _Engine:
             from ..ops import gemm
 
             gemm.set_backend(v)
+        elif k == "bigdl.decode.native":            # Transformer beam search on the KV-cache decode kernels
+            from ..ops import attention
+
+            attention.set_decode_native(v)
         elif k == "bigdl.module.deviceTiming":      # getTimes in device time (HIP events) for GPU modules
             from ..nn import abstractnn
 

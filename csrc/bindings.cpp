@@ -1513,6 +1513,66 @@ void attn_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const OptT& bia
   c.dq = mf(dq, "dq"); c.dk = mf(dk, "dk"); c.dv = mf(dv, "dv");
   TORCH_CHECK(bigdl_attn_bwd(&c, mf(delta_ws, "delta"), stream()) == 0, "attn_bwd: unsupported shape");
 }
+const int* oci32(const OptT& t, int64_t n, const char* name) {
+  if (!(t && t->defined())) return nullptr;
+  check(*t, at::kInt, name);
+  TORCH_CHECK(t->is_contiguous() && t->numel() == n, name, ": contiguous int32 of ", n, " entries");
+  return (const int*)t->data_ptr();
+}
+bool aligned16(const Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0; }
+void attn_decode(const Tensor& q, const Tensor& kcache, const Tensor& vcache, int64_t length, int64_t heads,
+                 const OptT& rows, const OptT& bias, const Tensor& o) {
+  TORCH_CHECK(q.dim() == 2 && kcache.dim() == 3 && kcache.sizes() == vcache.sizes() && o.sizes() == q.sizes(),
+              "attn_decode: q / o [N, hidden], kcache / vcache [R, Lmax, hidden]");
+  TORCH_CHECK(q.is_contiguous() && kcache.is_contiguous() && vcache.is_contiguous() && o.is_contiguous(),
+              "attn_decode: contiguous operands");
+  const int64_t N = q.size(0), hidden = q.size(1), R = kcache.size(0), Lmax = kcache.size(1);
+  TORCH_CHECK(N >= 1 && R >= 1 && kcache.size(2) == hidden && hidden % 8 == 0, "attn_decode: hidden size (% 8 == 0)");
+  TORCH_CHECK(heads >= 1 && hidden % heads == 0, "attn_decode: heads");
+  const int64_t D = hidden / heads;
+  TORCH_CHECK(D == 32 || D == 64 || D == 96 || D == 128, "attn_decode: head dim must be 32, 64, 96 or 128");
+  TORCH_CHECK(length >= 1 && length <= Lmax, "attn_decode: 1 <= length <= Lmax");
+  TORCH_CHECK(aligned16(q) && aligned16(kcache) && aligned16(vcache), "attn_decode: 16-byte aligned operands");
+  const bool has_rows = rows && rows->defined();
+  TORCH_CHECK(has_rows || N == R, "attn_decode: without rows the cache holds one row per sequence");
+  const float* b = nullptr;
+  if (bias && bias->defined()) {
+    TORCH_CHECK(bias->dim() == 2 && bias->size(0) == R && bias->size(1) == Lmax && bias->is_contiguous(),
+                "attn_decode: bias must be a contiguous [R, Lmax]");
+    b = cf(*bias, "bias");
+  }
+  TORCH_CHECK(bigdl_attn_decode(cf(q, "q"), cbf(kcache, "kcache"), cbf(vcache, "vcache"), oci32(rows, N, "rows"), b,
+                                mf(o, "o"), (int)N, (int)R, (int)Lmax, (int)heads, (int)D, (int)length,
+                                stream()) == 0, "attn_decode: unsupported shape");
+}
+void kv_append(const Tensor& k, const Tensor& v, const Tensor& kcache, const Tensor& vcache, int64_t pos) {
+  TORCH_CHECK(k.dim() == 2 && k.sizes() == v.sizes() && kcache.dim() == 3 && kcache.sizes() == vcache.sizes(),
+              "kv_append: k / v [N, hidden], kcache / vcache [N, Lmax, hidden]");
+  TORCH_CHECK(k.is_contiguous() && v.is_contiguous() && kcache.is_contiguous() && vcache.is_contiguous(),
+              "kv_append: contiguous operands");
+  TORCH_CHECK(kcache.size(0) == k.size(0) && kcache.size(2) == k.size(1) && k.size(1) % 8 == 0 && k.size(0) >= 1,
+              "kv_append: shapes (hidden % 8 == 0)");
+  TORCH_CHECK(pos >= 0 && pos < kcache.size(1), "kv_append: 0 <= pos < Lmax");
+  TORCH_CHECK(aligned16(k) && aligned16(v) && aligned16(kcache) && aligned16(vcache), "kv_append: 16-byte alignment");
+  TORCH_CHECK(bigdl_kv_append(cf(k, "k"), cf(v, "v"), mbf(kcache, "kcache"), mbf(vcache, "vcache"), (int)k.size(0),
+                              (int)kcache.size(1), (int)k.size(1), (int)pos, stream()) == 0, "kv_append: unsupported shape");
+}
+// src / dst [..., N, Lmax, hidden] (the leading dimensions are the (layer, k / v) planes), parent int32 [N]
+void kv_reorder(const Tensor& src, const Tensor& dst, const Tensor& parent, int64_t length) {
+  TORCH_CHECK(src.dim() >= 3 && src.sizes() == dst.sizes() && src.is_contiguous() && dst.is_contiguous(),
+              "kv_reorder: src / dst contiguous [..., N, Lmax, hidden] of one shape");
+  const int64_t nd = src.dim(), N = src.size(nd - 3), Lmax = src.size(nd - 2), hidden = src.size(nd - 1);
+  TORCH_CHECK(N >= 1 && Lmax >= 1 && hidden >= 8 && hidden % 8 == 0, "kv_reorder: hidden % 8 == 0");
+  TORCH_CHECK(length >= 1 && length <= Lmax, "kv_reorder: 1 <= length <= Lmax");
+  const int64_t bytes = src.numel() * 2;
+  const char* s = (const char*)src.data_ptr();
+  const char* d = (const char*)dst.data_ptr();
+  TORCH_CHECK(s + bytes <= d || d + bytes <= s, "kv_reorder: never in place (src and dst overlap)");
+  TORCH_CHECK(aligned16(src) && aligned16(dst), "kv_reorder: 16-byte alignment");
+  TORCH_CHECK(bigdl_kv_reorder(cbf(src, "src"), mbf(dst, "dst"), oci32(parent, N, "parent"),
+                               (int)(src.numel() / (N * Lmax * hidden)), (int)N, (int)Lmax, (int)hidden, (int)length,
+                               stream()) == 0, "kv_reorder: unsupported shape");
+}
 // geo = [stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups]
 void gconv(int64_t pass, const Tensor& x_or_dx, const Tensor& w_or_dw, const OptT& b_or_db, const Tensor& y_or_dy,
            std::vector<int64_t> geo) {
@@ -1748,6 +1808,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"), py::arg("H"),
         py::arg("causal"), py::arg("o"), py::arg("lse"), py::arg("mlog"), py::arg("drop_p") = 0.0, py::arg("seed") = 0);
   m.def("gconv", &gconv);
+  m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("kcache"), py::arg("vcache"), py::arg("length"),
+        py::arg("heads"), py::arg("rows"), py::arg("bias"), py::arg("o"));
+  m.def("kv_append", &kv_append);
+  m.def("kv_reorder", &kv_reorder);
   m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"), py::arg("H"),
         py::arg("causal"), py::arg("o"), py::arg("mlog"), py::arg("dout"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
         py::arg("delta_ws"), py::arg("drop_p") = 0.0, py::arg("seed") = 0);

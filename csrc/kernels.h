@@ -426,6 +426,19 @@ typedef struct {
 int bigdl_attn_fwd(const AttnCall* c, hipStream_t st);
 int bigdl_attn_bwd(const AttnCall* c, float* delta_ws, hipStream_t st);
 
+// Single-token attention decode and KV-cache maintenance (csrc/attn_decode.hip). q / o fp32 [N][heads * D] (q already
+// scaled; rounded to bf16 on load), kcache / vcache bf16 [R][Lmax][heads * D], keys 0..len-1 valid, rows (optional,
+// int32 [N]) the cache row of sequence n (clamped to [0, R)), bias (optional) fp32 [R][Lmax] read through the same
+// rows. D = 32, 64, 96 or 128. kv_append writes the fp32 rows k, v [N][hidden] to position pos of both caches
+// ([N][Lmax][hidden]) as bf16. kv_reorder: dst[x][n][0..len) = src[x][parent[n]][0..len) over planes x of
+// [N][Lmax][hidden] (src != dst). Return -1 on an unsupported argument.
+int bigdl_attn_decode(const float* q, const uint16_t* kcache, const uint16_t* vcache, const int* rows,
+                      const float* bias, float* o, int N, int R, int Lmax, int heads, int D, int len, hipStream_t st);
+int bigdl_kv_append(const float* k, const float* v, uint16_t* kcache, uint16_t* vcache, int N, int Lmax, int hidden,
+                    int pos, hipStream_t st);
+int bigdl_kv_reorder(const uint16_t* src, uint16_t* dst, const int* parent, int planes, int N, int Lmax, int hidden,
+                     int len, hipStream_t st);
+
 // Adaptive OptimMethod updates on flat fp32 buffers (csrc/optim.hip): method 0 Adagrad (a = lr, b = weight decay),
 // 1 RMSprop (a = lr, b = decay rate, c = eps), 2 Adadelta (a = decay rate, b = eps), 3 Adamax (a = lr / (1 - b1^t),
 // b = b1, c = b2, d = eps), 4 Ftrl (a = lr, b = lr power, c = l1, d = l2, e = l2 shrinkage); s1 / s2 are the state
