@@ -194,7 +194,27 @@ class SpatialConvolution(TensorModule):
         self._geom = (x.shape, ph, pw)
         return y
 
-    def _wgrad_gpu_pairs(self, x, gy16):
+    def _takes_bn_grad_pre(self, gz, y):
+        """Asked by the training BN + ReLU that consumes this convolution's output ``y`` (nn.normalization
+        backward_fused): True when the weight gradient is this module's only backward work and runs the pair-view stem
+        kernel, which forms the BN's input gradient on load from the BN's output gradient ``gz`` (a tensor tagged
+        ``_bn_grad_pre``) instead of reading a materialised one."""
+        xpair = getattr(self, "_xpair", None)
+        if (xpair is None or self.propagateBack or self._frozen or self.fuse_relu or self.nGroup != 1
+                or self.format != "NCHW" or self.gradWeight.dtype != torch.float32
+                or type(self)._wgrad_gpu is not SpatialConvolution._wgrad_gpu
+                or type(self).accGradParameters is not SpatialConvolution.accGradParameters
+                or y is not self.output or not (gz.is_cuda and gz.dtype == BF16 and gz.shape == y.shape
+                                                and gz.stride() == y.stride())):
+            return False
+        xp = xpair[0]
+        K = self.nOutputPlane
+        if y.shape[0] != xp.shape[0] or y.shape[1] != K or y.dtype != BF16:
+            return False
+        return cv.pairs_wgrad_takes_bn_pre(xp, K, y.shape[2], y.shape[3], self.kernelH, (self.kernelW + 1) // 2,
+                                           self.strideH, self.bias is not None)
+
+    def _wgrad_gpu_pairs(self, x, gy16, bn_pre=None):
         xp, shape, ph, pw = self._xpair
         R, S, K = self.kernelH, self.kernelW, self.nOutputPlane
         S2 = (S + 1) // 2
@@ -202,7 +222,7 @@ class SpatialConvolution(TensorModule):
         db = None
         if self.bias is not None:
             db = self.gradBias if self.scaleB == 1.0 else ops.zeros(K, device=x.device)
-        cv.conv2d_pairs_wgrad(gy16, xp, R, S2, self.strideH, dwp, db)
+        cv.conv2d_pairs_wgrad(gy16, xp, R, S2, self.strideH, dwp, db, bn_pre=bn_pre)
         ops.native.get().pair_wgrad_add(dwp, self.gradWeight, float(self.scaleW))
         if db is not None and db is not self.gradBias:
             self.gradBias.add_(db, alpha=self.scaleB)
@@ -407,11 +427,16 @@ class SpatialConvolution(TensorModule):
 
     def _wgrad_gpu(self, x, gy, ph, pw):
         gy16 = gy if (gy.dtype == BF16 and gy.is_contiguous(memory_format=CL)) else gy.to(BF16, memory_format=CL)
+        # the consumer BN's output gradient plus its backward coefficients (_takes_bn_grad_pre said yes)
+        bn_pre = getattr(gy, "_bn_grad_pre", None)
         xpair = getattr(self, "_xpair", None)
         if (xpair is not None and xpair[1] == tuple(x.shape) and xpair[2:] == (ph, pw) and self.nGroup == 1
-                and self.gradWeight.dtype == torch.float32):
-            self._wgrad_gpu_pairs(x, gy16)
+                and self.gradWeight.dtype == torch.float32 and (bn_pre is None or gy16 is gy)):
+            self._wgrad_gpu_pairs(x, gy16, bn_pre)
             return
+        if bn_pre is not None:
+            raise RuntimeError("SpatialConvolution: a BN backward to apply on load reached a weight gradient other "
+                               "than the pair-view stem kernel's")
         x16 = getattr(self, "_x16", None)
         pre = None
         if x16 is None or x16.shape[0] != x.shape[0] or x16.shape[2:] != x.shape[2:]:

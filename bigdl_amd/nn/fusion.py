@@ -14,7 +14,12 @@ work the producer already did.
                       reduction pass
   ResNet block        Sequential[ConcatTable[branch(... BN), shortcut], CAddTable, ReLU]: the shortcut runs
                       first, its output is added inside the branch's last BN apply pass together with the
-                      ReLU; backward emits the residual-branch gradient from the same pass.
+                      ReLU; backward emits the residual-branch gradient from the same pass. A projection shortcut's
+                      BN hands over its input and affine instead of an output (its apply runs inside that pass),
+                      and in backward takes the block's output gradient under the block BN's sign mask instead of
+                      a stored residual-branch gradient.
+  stem conv -> BN     (a convolution without data gradient) the BN's backward gives its coefficients to the stem's
+                      weight gradient, which forms the BN's input gradient on load.
 """
 import os
 
@@ -47,7 +52,7 @@ def _reset(m):
             x._graph_dres = False
     for x in m.flattened_layers():
         for attr, val in (("emit_stats", False), ("fuse_relu", False), ("passthrough", False),
-                          ("_dgrad_bn_ok", False), ("_defer_ok", False)):
+                          ("_dgrad_bn_ok", False), ("_defer_ok", False), ("_grad_to", None)):
             if hasattr(x, attr):
                 setattr(x, attr, val)
         if isinstance(x, Sequential):
@@ -213,6 +218,10 @@ def _fuse_sequential(seq):
     for a, b in zip(mods[:-1], mods[1:]):
         if isinstance(a, SpatialConvolution) and isinstance(b, BatchNormalization) and a.nGroup == 1:
             a.emit_stats = True
+            if not a.propagateBack:
+                # the BN's input gradient has one reader, this convolution's weight gradient: where that is the
+                # pair-view stem kernel, the BN hands it its backward coefficients instead of running its apply pass
+                b._grad_to = a
         elif isinstance(a, BatchNormalization) and isinstance(b, ReLU):
             a.fuse_relu = True
             b.passthrough = True
@@ -262,10 +271,43 @@ def _plan_deferred_bn(a, b, c):
         a._defer_ok = True
 
 
+# BIGDL_SHORTCUT_FOLD=0: the projection shortcut's BN runs its own apply pass (writes its output, which the block's
+# last BN reads back as the residual) instead of handing its input and affine to that BN's apply pass
+SHORTCUT_FOLD = [os.environ.get("BIGDL_SHORTCUT_FOLD", "1") != "0"]
+
+# BIGDL_SHORTCUT_NODRES=0: a projection block's residual gradient (the output gradient under the block BN's sign mask)
+# is materialised for the shortcut BN's backward instead of being masked there on load
+SHORTCUT_NODRES = [os.environ.get("BIGDL_SHORTCUT_NODRES", "1") != "0"]
+
+
+def _shortcut_fold_bn(short, x):
+    """The last BN of a ``Sequential(..., BN)`` projection shortcut when its apply pass can be folded into the block's
+    last BN apply pass (csrc/batchnorm.hip bn_apply_kernel RA): a training BN without ReLU on the GPU engine. The BN
+    itself checks what only it can see (its input's dtype / layout, sync-BN) and falls back to a real output, and the
+    block BN materialises a deferred residual it cannot read as it is, so a miss here or there costs the pass only.
+    The shortcut's ``output`` is then a deferred tensor (ops/bn.py deferred(relu=False)): inside the plan only the
+    block BN reads it; any other reader goes through ``ops.bn.materialize``."""
+    if not (SHORTCUT_FOLD[0] and isinstance(short, Sequential) and len(short.modules) >= 2
+            and short._residual_plan is None and torch.is_tensor(x) and x.is_cuda):
+        return None
+    sbn = short.modules[-1]
+    if not (isinstance(sbn, BatchNormalization) and sbn.train and not sbn.fuse_relu and sbn.nOutput % 8 == 0
+            and sbn.sync_fn is None and sbn.dataFormat == "NCHW"):
+        return None
+    return sbn
+
+
 def residual_forward(seq, x):
     branch, short, bn = seq._residual_plan
     concat, add, relu = seq.modules
-    res = short.forward(x)
+    sbn = _shortcut_fold_bn(short, x)
+    if sbn is not None:
+        sbn._fold_once = True
+    try:
+        res = short.forward(x)
+    finally:
+        if sbn is not None:
+            sbn.__dict__.pop("_fold_once", None)
     h = x
     for m in branch.modules[:-1]:
         h = m.forward(h)
@@ -366,7 +408,17 @@ def residual_backward(seq, x, gradOutput):
                 from ..ops import bn as bnops
 
                 sec = (xs, sbn.saveMean, bnops.new_stats(xs.shape[1], xs.device))
-        dh, dres = bn.backward_fused(seq._res_h, gradOutput, need_dres=True, sec=sec)
+        # with the sign mask at hand dres is not written either: its one reader, the shortcut BN's backward, masks the
+        # block's output gradient on load, as the identity blocks' first dgrad does (one bf16 write pass less)
+        nodres = (SHORTCUT_NODRES[0] and sec is not None and zm is not None and bn.train and xs.dim() == 4
+                  and torch.is_tensor(gradOutput) and gradOutput.is_cuda and tuple(gradOutput.shape) == tuple(xs.shape))
+        dh, dres = bn.backward_fused(seq._res_h, gradOutput, need_dres=not nodres, sec=sec)
+        if nodres:
+            dres = gradOutput
+            if dres.dtype != torch.bfloat16 or dres.stride() != xs.stride():
+                dres = dres.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+            dres = dres.detach()
+            dres._bn_gmask = zm
         if sec is not None:
             dres._bn_red = (sbn, sec[2])
         # shortcut first, so its gradient can be summed inside the epilogue of the branch's first dgrad GEMM

@@ -25,12 +25,17 @@ _ZMASK = os.environ.get("BIGDL_BN_ZMASK", "1") != "0"
 # BIGDL_BN_DEFER=0: always materialise a training BN + ReLU output, even where nn.fusion found a consumer that applies
 # it on load (ConvArgs::pre). See nn.fusion._defer_consumer for which consumers each level defers to.
 _DEFER = [os.environ.get("BIGDL_BN_DEFER", "1") != "0"]
+# BIGDL_STEM_BNPRE=0: the stem BN's backward always runs its apply pass and hands the stem convolution a materialised
+# gradient, instead of handing its coefficients to the stem weight gradient (backward_fused)
+_STEM_BNPRE = os.environ.get("BIGDL_STEM_BNPRE", "1") != "0"
 CL = torch.channels_last
 BF16 = torch.bfloat16
 
 
 class BatchNormalization(TensorModule):
     """BN over dim 2 (1-based) of (N, C) or (N, C, H, W) input."""
+
+    _grad_to = None     # nn.fusion: the convolution right before this BN when it has no data gradient (an image stem)
 
     def __init__(self, nOutput, eps=1e-5, momentum=0.1, affine=True, initWeight=None, initBias=None,
                  initGradWeight=None, initGradBias=None, dataFormat="NCHW"):
@@ -108,9 +113,26 @@ class BatchNormalization(TensorModule):
     def updateOutput(self, input, residual=None):
         if residual is None:     # a Graph's fused residual add (nn.fusion._fuse_graph_training)
             residual = self.__dict__.pop("_graph_residual", None)
+        # nn.fusion.residual_forward asks a projection shortcut's last BN (one call) to skip its apply pass
+        fold = self.__dict__.pop("_fold_once", False)
         x = self._to_nchw(input)
+        # a residual that is such a shortcut BN's un-applied input (ops/bn.py deferred(relu=False)) is applied in this
+        # BN's apply pass when it can be read as it is, else materialised first
+        res_aff = getattr(residual, "_bn_lin", None)
+        if res_aff is not None and not (self._gpu_ok(x) and residual.dtype == BF16 and x.dtype == BF16
+                                        and residual.stride() == x.stride()):
+            residual, res_aff = bnops.materialize(residual), None
         if self._gpu_ok(x):
             stats = getattr(input, "_bn_stats", None) if self.train else None
+            if (fold and self.train and not self.fuse_relu and residual is None and self.sync_fn is None
+                    and x.dim() == 4 and self.dataFormat == "NCHW" and x.dtype == BF16
+                    and x.is_contiguous(memory_format=CL)):
+                # statistics (from the conv epilogue) and finalize only; the consumer adds bf16(x * scale + shift)
+                sm, si, aff = bnops.bn_prepare_gpu(x, self.weight, self.bias, self.runningMean, self.runningVar,
+                                                   self.eps, self.momentum, stats=stats)
+                self.saveMean, self.saveStd = sm, si
+                self._aff, self._zm, self._xin = None, None, x
+                return bnops.deferred(x, aff, relu=False)
             x = self._prep_gpu(x)
             res = residual
             if res is not None and (res.dtype != BF16 or res.stride() != x.stride()):
@@ -134,7 +156,7 @@ class BatchNormalization(TensorModule):
             y, sm, si, aff = bnops.bn_forward_gpu(x, self.weight, self.bias, self.runningMean, self.runningVar,
                                                    self.eps, self.momentum, self.train, stats=stats, res=res,
                                                    relu=self.fuse_relu, sync_fn=self.sync_fn if self.train else None,
-                                                   zm=zm)
+                                                   zm=zm, res_aff=res_aff)
             self.saveMean, self.saveStd = sm, si
             # without a residual the ReLU mask is a function of x: backward recomputes it from (scale, shift)
             self._aff = aff if (self.fuse_relu and res is None) else None
@@ -172,16 +194,39 @@ class BatchNormalization(TensorModule):
         aff = getattr(self, "_aff", None)
         zm = getattr(self, "_zm", None)
         z = self._to_nchw(self.output) if (self.fuse_relu and aff is None and zm is None) else None
+        # the output gradient is gradOutput under another BN's sign mask (nn.fusion.residual_backward: a projection
+        # shortcut's BN takes the block's output gradient and the block BN's mask, not a materialised product)
+        gmask = getattr(gradOutput, "_bn_gmask", None)
+        if gmask is not None:
+            if self.fuse_relu:
+                raise ValueError("BatchNormalization: a masked output gradient needs a BN without fused ReLU")
+            z, aff, zm = None, None, gmask
         direct = self._direct_grads()
         dg = self.gradWeight if direct else (torch.zeros_like(self.runningMean) if self.affine else None)
         db = self.gradBias if direct else (torch.zeros_like(self.runningMean) if self.affine else None)
         pre = getattr(gradOutput, "_bn_red", None)
         red = pre[1] if (pre is not None and pre[0] is self and self.train) else None
         graph_res = getattr(self, "_graph_dres", False)
-        dx, dres = bnops.bn_backward_gpu(gz, z, x, self.saveMean, self.saveStd, self.weight, dg, db,
-                                         training=self.train, need_dres=need_dres or graph_res,
-                                         sync_fn=self.sync_fn if self.train else None, aff=aff, red=red, zm=zm,
-                                         sec=sec)
+        conv = self._grad_to
+        if (_STEM_BNPRE and conv is not None and red is not None and self.sync_fn is None and aff is not None
+                and z is None and zm is None and not need_dres and sec is None and not graph_res and x.dim() == 4
+                and self.dataFormat == "NCHW" and gz.is_contiguous(memory_format=CL)
+                and not ops.native.deterministic() and conv._takes_bn_grad_pre(gz, x)):
+            # the producer is the pair-view stem convolution, which has no data gradient: its weight gradient is the
+            # only reader of dx, so only the coefficients (and dgamma / dbeta) are computed here and the weight
+            # gradient forms dx = A * mask(dz) + B * x + D on load (csrc/stem_fwd.hip stem_wgrad_kernel PRE): the
+            # largest BN backward apply pass of a ResNet step is neither run nor its result written and read back.
+            # (Not in deterministic mode, where the bias gradient is a column sum over a materialised dx.)
+            coef = torch.empty(3 * x.shape[1], dtype=torch.float32, device=x.device)
+            bnops.bn_backward_gpu(gz, None, x, self.saveMean, self.saveStd, self.weight, dg, db, training=True,
+                                  need_dx=False, aff=aff, red=red, coef=coef)
+            dx, dres = gz.detach(), None
+            dx._bn_grad_pre = (x, coef, aff)
+        else:
+            dx, dres = bnops.bn_backward_gpu(gz, z, x, self.saveMean, self.saveStd, self.weight, dg, db,
+                                             training=self.train, need_dres=need_dres or graph_res,
+                                             sync_fn=self.sync_fn if self.train else None, aff=aff, red=red, zm=zm,
+                                             sec=sec)
         if graph_res:
             self._dres = dres
         if not direct and self.affine and not self._frozen:

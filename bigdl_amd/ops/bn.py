@@ -69,8 +69,11 @@ def _reduce_slots_for_sync(buf, C, P, sync_fn):
 
 
 def bn_forward_gpu(x, gamma, beta, rmean, rvar, eps, momentum, training, stats=None, res=None, relu=False,
-                   out=None, sync_fn=None, zm=None):
+                   out=None, sync_fn=None, zm=None, res_aff=None):
     """Returns (y, save_mean, save_invstd, aff) with aff = [scale | shift] of the apply pass (fp32 [2C]).
+
+    ``res_aff`` (optional, fp32 [2C] = [scale | shift]): ``res`` is the un-applied input of a ReLU-less BN (a projection
+    shortcut's, see ``deferred``); the apply pass adds bf16(res * scale + shift), bit-equal to applying that BN first.
 
     ``zm`` (optional, uint8 [P * C / 8]) receives the sign mask of y (bit e of byte (p, g): y[p][8g + e] > 0), which
     the backward passes read in place of y itself (csrc/batchnorm.hip: 1/16 of the bytes).
@@ -100,7 +103,10 @@ def bn_forward_gpu(x, gamma, beta, rmean, rvar, eps, momentum, training, stats=N
         stats, nslots = scale, 0  # unused in inference mode
     C_.bn_finalize(stats, nslots, gamma, beta, rmean, rvar, smean, sinv, scale, shift, Ptot, C, float(eps),
                    float(momentum), bool(training))
-    C_.bn_apply(x, scale, shift, res, out, P, C, bool(relu), zm)
+    if res_aff is not None:
+        C_.bn_apply(x, scale, shift, res, out, P, C, bool(relu), zm, res_aff[:C], res_aff[C:])
+    else:
+        C_.bn_apply(x, scale, shift, res, out, P, C, bool(relu), zm)
     return out, smean, sinv, aff
 
 
@@ -126,28 +132,35 @@ def bn_prepare_gpu(x, gamma, beta, rmean, rvar, eps, momentum, stats=None, sync_
     return smean, sinv, aff
 
 
-def deferred(x, aff):
+def deferred(x, aff, relu=True):
     """A deferred BN + ReLU output: a new tensor object over x's storage tagged with ``_bn_pre`` = aff. Only a
-    consumer that applies it (or ``materialize``) may read it; nn.fusion hands it to such consumers only."""
+    consumer that applies it (or ``materialize``) may read it; nn.fusion hands it to such consumers only.
+    ``relu=False``: a deferred ReLU-less BN output (a projection shortcut's, added by the block's last BN apply pass),
+    tagged with ``_bn_lin`` instead, so that no ``_bn_pre`` consumer mistakes it for a BN + ReLU one."""
     y = x.detach()
-    y._bn_pre = aff
+    if relu:
+        y._bn_pre = aff
+    else:
+        y._bn_lin = aff
     return y
 
 
 def materialize(t):
-    """The real values of a deferred BN + ReLU output (bn_apply into a new tensor on the current stream); any
+    """The real values of a deferred BN (+ ReLU) output (bn_apply into a new tensor on the current stream); any
     other tensor is returned as is."""
-    aff = getattr(t, "_bn_pre", None)
+    aff, relu = getattr(t, "_bn_pre", None), True
+    if aff is None:
+        aff, relu = getattr(t, "_bn_lin", None), False
     if aff is None:
         return t
     C = t.shape[1]
     y = torch.empty_like(t)
-    native.get().bn_apply(t, aff[:C], aff[C:], None, y, _P(t), C, True)
+    native.get().bn_apply(t, aff[:C], aff[C:], None, y, _P(t), C, relu)
     return y
 
 
 def bn_backward_gpu(dz, z, x, smean, sinv, gamma, dgamma, dbeta, training=True, need_dres=False, need_dx=True,
-                    sync_fn=None, aff=None, red=None, zm=None, sec=None):
+                    sync_fn=None, aff=None, red=None, zm=None, sec=None, coef=None):
     """Backward of y = relu?(bn(x) [+ res]).
 
     dz: gradient w.r.t. the (post-relu) output; z: the forward output (ReLU mask) or None. With z None and
@@ -156,7 +169,11 @@ def bn_backward_gpu(dz, z, x, smean, sinv, gamma, dgamma, dbeta, training=True, 
     ``red``: the slotted backward reduction already accumulated by the producer of dz (a dgrad epilogue).
     ``zm``: the forward's sign mask of the output (bn_forward_gpu), used in place of z.
     ``sec``: (x2, mean2, red2) of a second training BN without ReLU whose output gradient is dres (a projection
-    shortcut): its slotted backward reduction is accumulated into red2 by the same pass (requires need_dres).
+    shortcut): its slotted backward reduction is accumulated into red2 by the same pass. With ``need_dres`` False
+    the sums are taken all the same and dres is not written: that BN's backward then takes (dz, zm) in its place.
+    ``coef`` (optional, fp32 [3C]): receives the coefficients A | B | D of dx = A * mask(dz) + B * x + D. With
+    ``need_dx`` False only they (and dgamma / dbeta) are computed, for a consumer that applies them on load
+    (ops/conv.py conv2d_pairs_wgrad ``bn_pre``).
     """
     C = x.shape[1]
     P = _P(x)
@@ -171,10 +188,11 @@ def bn_backward_gpu(dz, z, x, smean, sinv, gamma, dgamma, dbeta, training=True, 
         nslots = stat_slots()
         if sync_fn is not None:
             red, nslots, Ptot = _reduce_slots_for_sync(red, C, P, sync_fn)
-    coef = torch.empty(3 * C, dtype=torch.float32, device=x.device)
+    if coef is None:
+        coef = torch.empty(3 * C, dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x) if need_dx else None
     dres = torch.empty_like(x) if need_dres else None
-    if sec is not None and dres is not None and training:
+    if sec is not None and training:
         x2, mean2, red2 = sec
         C_.bn_bwd_apply(dz, z, x, smean, sinv, gamma, red, nslots, coef, dx, dres, dgamma, dbeta, Ptot, C, aff, zm,
                         x2=x2, mean2=mean2, red2=red2)

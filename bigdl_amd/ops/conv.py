@@ -461,11 +461,30 @@ def conv2d_pairs_fwd(xp, wp, bias, K, OH, OW, R, S2, sh, relu=False, stats=None)
     return out
 
 
-def conv2d_pairs_wgrad(dy, xp, R, S2, sh, dwp32, dbias32):
-    """dW' (fp32 (K, R * S2 * 8)) += weight gradient of the pair view; dbias += sum(dy)."""
+def _pairs_wgrad_geo(N, Hp, Wq, K, OH, OW, R, S2, sh):
+    return [N, Hp, Wq, 8, OH, OW, R, S2, sh, 1, 0, 0, 1, 1, N * OH * OW, K, R * S2 * 8, K]
+
+
+def pairs_wgrad_takes_bn_pre(xp, K, OH, OW, R, S2, sh, bias):
+    """True when conv2d_pairs_wgrad runs the pair-view stem kernel on this geometry, the one kernel that forms its
+    output gradient on load from the consumer BN's backward (``bn_pre``)."""
+    N, Hp, Wq, _ = xp.shape
+    return native.get().conv_wgrad_plan_info(_pairs_wgrad_geo(N, Hp, Wq, K, OH, OW, R, S2, sh), bool(bias))[0] == -1
+
+
+def conv2d_pairs_wgrad(dy, xp, R, S2, sh, dwp32, dbias32, bn_pre=None):
+    """dW' (fp32 (K, R * S2 * 8)) += weight gradient of the pair view; dbias += sum(dy).
+
+    ``bn_pre`` = (x, coef, aff): ``dy`` is the output gradient dz of the training BN + ReLU whose input x this
+    convolution produced, and the convolution's own output gradient A * mask(dz) + B * x + D (coef = A | B | D, mask =
+    x * aff[:K] + aff[K:] > 0) is formed on load instead of being read (csrc/stem_fwd.hip stem_wgrad_kernel PRE): ask
+    ``pairs_wgrad_takes_bn_pre`` first, any other kernel refuses it."""
     N, Hp, Wq, _ = xp.shape
     _, K, OH, OW = dy.shape
-    geo = [N, Hp, Wq, 8, OH, OW, R, S2, sh, 1, 0, 0, 1, 1, N * OH * OW, K, R * S2 * 8, K]
+    geo = _pairs_wgrad_geo(N, Hp, Wq, K, OH, OW, R, S2, sh)
+    if bn_pre is not None:
+        native.get().conv_wgrad(dy, xp, dwp32, dbias32, geo, None, bn_pre[0], bn_pre[1], bn_pre[2])
+        return
     native.get().conv_wgrad(dy, xp, dwp32, dbias32, geo)
 
 

@@ -182,14 +182,23 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats, int nslots, 
   shift[c] = b - mean * g * invstd;
 }
 
+__device__ __forceinline__ void load8(const float* p, float* v) {
+  const v4f a = *reinterpret_cast<const v4f*>(p), b = *reinterpret_cast<const v4f*>(p + 4);
+  v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+}
+
 // Channel-stationary mapping (also bn_bwd_apply_kernel): a thread owns one 8-channel group for its whole row
 // range, so its per-channel coefficients are loaded once instead of once per 16-byte granule, and the loop has
 // no 64-bit modulo. blockIdx.y walks channel groups in chunks of 256; rows of a block are [rbeg, rend).
-template <int U>
+// RA: the residual is itself the un-applied input of a ReLU-less BN (a projection shortcut's): res * res_scale + res_shift
+// is rounded to bf16 before the add, which is what that BN's own apply pass would have stored, so y and zm are
+// bit-equal to the two-pass form and the shortcut's output is never written or read back.
+template <int U, bool RA>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_t* __restrict__ x, const float* __restrict__ scale,
                                                        const float* __restrict__ shift, const bf16_t* __restrict__ res,
                                                        bf16_t* __restrict__ y, long P, int C, long rpb, int relu,
-                                                       uint8_t* __restrict__ zm) {
+                                                       uint8_t* __restrict__ zm, const float* __restrict__ res_scale,
+                                                       const float* __restrict__ res_shift) {
   const int G = C >> 3;
   const int gbase = blockIdx.y * 256;
   const int gcount = min(256, G - gbase);
@@ -202,6 +211,11 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_t* __restrict_
   const v4f b0 = *reinterpret_cast<const v4f*>(shift + c0), b1 = *reinterpret_cast<const v4f*>(shift + c0 + 4);
   const float sc[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
   const float sh[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+  float rsc[8], rsh[8];
+  if (RA) {
+    load8(res_scale + c0, rsc);
+    load8(res_shift + c0, rsh);
+  }
   for (long r0 = rbeg + rsub; r0 < rend; r0 += (long)U * rpi) {
     v4u vx[U], vr[U];
 #pragma unroll
@@ -220,7 +234,11 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_t* __restrict_
       for (int e = 0; e < 4; ++e) {
         float l = lo_bf(vx[u][e]) * sc[2 * e] + sh[2 * e];
         float h = hi_bf(vx[u][e]) * sc[2 * e + 1] + sh[2 * e + 1];
-        if (res) { l += lo_bf(vr[u][e]); h += hi_bf(vr[u][e]); }
+        if (RA) {
+          const unsigned q = pack2bf(lo_bf(vr[u][e]) * rsc[2 * e] + rsh[2 * e],
+                                     hi_bf(vr[u][e]) * rsc[2 * e + 1] + rsh[2 * e + 1]);
+          l += lo_bf(q); h += hi_bf(q);
+        } else if (res) { l += lo_bf(vr[u][e]); h += hi_bf(vr[u][e]); }
         if (relu) { l = fmaxf(l, 0.f); h = fmaxf(h, 0.f); }
         o[e] = pack2bf(l, h);
       }
@@ -263,11 +281,6 @@ __global__ void bn_slot_reduce_kernel(const float* __restrict__ in, int nslots, 
   float t = 0.f;
   for (int k = 0; k < nslots; ++k) t += in[(size_t)k * 2 * C + c];
   out[c] = t;
-}
-
-__device__ __forceinline__ void load8(const float* p, float* v) {
-  const v4f a = *reinterpret_cast<const v4f*>(p), b = *reinterpret_cast<const v4f*>(p + 4);
-  v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
 }
 
 // R2: the residual-branch gradient dres (= masked dz) is also the output gradient of a second training BN without
@@ -332,13 +345,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restr
         float d0 = lo_bf(vd[u][e]), d1 = hi_bf(vd[u][e]);
         const float x0 = lo_bf(vx[u][e]), x1 = hi_bf(vx[u][e]);
         if (z || zm) { if (!(lo_bf(vz[u][e]) > 0.f)) d0 = 0.f; if (!(hi_bf(vz[u][e]) > 0.f)) d1 = 0.f; }
-        if (xmask) {
-          if (!(x0 * S[2 * e] + T[2 * e] > 0.f)) d0 = 0.f;
-          if (!(x1 * S[2 * e + 1] + T[2 * e + 1] > 0.f)) d1 = 0.f;
-        }
-        const float r0v = A[2 * e] * d0 + B[2 * e] * x0 + D[2 * e];
-        const float r1v = A[2 * e + 1] * d1 + B[2 * e + 1] * x1 + D[2 * e + 1];
-        o[e] = pack2bf(r0v, r1v);
+        o[e] = bn_bwd_pair(d0, d1, x0, x1, xmask, A[2 * e], A[2 * e + 1], B[2 * e], B[2 * e + 1], D[2 * e],
+                           D[2 * e + 1], S[2 * e], S[2 * e + 1], T[2 * e], T[2 * e + 1]);
         od[e] = pack2bf(d0, d1);
         if (R2 && r < rend) {
           const float q0 = lo_bf(od[e]), q1 = hi_bf(od[e]);
@@ -440,15 +448,22 @@ void bigdl_bn_slot_reduce(const float* in, int nslots, int C, float* out, hipStr
 }
 
 void bigdl_bn_apply(const uint16_t* x, const float* scale, const float* shift, const uint16_t* res, uint16_t* y,
-                    long P, int C, int relu, hipStream_t st, uint8_t* zm) {
+                    long P, int C, int relu, hipStream_t st, uint8_t* zm, const float* res_scale,
+                    const float* res_shift) {
   long rpb = 0;
   const dim3 grid = stationary_grid(P, C, &rpb);
+#define BN_APPLY(UU)                                                                                                   \
+  if (res && res_scale && res_shift)                                                                                   \
+    bn_apply_kernel<UU, true><<<grid, 256, 0, st>>>(x, scale, shift, res, y, P, C, rpb, relu, zm, res_scale, res_shift); \
+  else                                                                                                                 \
+    bn_apply_kernel<UU, false><<<grid, 256, 0, st>>>(x, scale, shift, res, y, P, C, rpb, relu, zm, nullptr, nullptr)
   switch (bn_unroll()) {
-    case 1: bn_apply_kernel<1><<<grid, 256, 0, st>>>(x, scale, shift, res, y, P, C, rpb, relu, zm); break;
-    case 2: bn_apply_kernel<2><<<grid, 256, 0, st>>>(x, scale, shift, res, y, P, C, rpb, relu, zm); break;
-    case 8: bn_apply_kernel<8><<<grid, 256, 0, st>>>(x, scale, shift, res, y, P, C, rpb, relu, zm); break;
-    default: bn_apply_kernel<4><<<grid, 256, 0, st>>>(x, scale, shift, res, y, P, C, rpb, relu, zm); break;
+    case 1: BN_APPLY(1); break;
+    case 2: BN_APPLY(2); break;
+    case 8: BN_APPLY(8); break;
+    default: BN_APPLY(4); break;
   }
+#undef BN_APPLY
   HIP_LAUNCH_CHECK();
 }
 
@@ -466,10 +481,10 @@ void bigdl_bn_bwd_apply(const uint16_t* dz, const uint16_t* z, const uint16_t* x
   const bf16_t* x2 = reinterpret_cast<const bf16_t*>(x2u);
   bn_bwd_coeff_kernel<<<(C + 7) / 8, 256, 0, st>>>(red, nslots, mean, invstd, gamma, coef, dgamma, dbeta, P, C,
                                                     training);
-  if (dx || dres) {
+  if (dx || dres || red2) {
     long rpb = 0;
     const dim3 grid = stationary_grid(P, C, &rpb);
-    if (red2) {        // second BN's reduction over dres (needs dres)
+    if (red2) {        // second BN's reduction over dres (dres itself may be null: its only reader masks dz instead)
 #define BWD2(UU) bn_bwd_apply_kernel<UU, true><<<grid, 256, 0, st>>>(dz, z, x, coef, dx, dres, P, C, rpb, aff, zm, x2, mean2, red2)
       switch (bn_unroll()) {
         case 1: BWD2(1); break;

@@ -216,10 +216,12 @@ bool conv_addend_stride_applies(std::vector<int64_t> geo, std::vector<int64_t> t
 // geo = [Nb, Hs, Ws, Cs, OH, OW, R, S, sh, sw, ph, pw, dh, dw, M, Ncol, Kdim, ldy]
 // pre: optional [2 Cs] scale | shift of the training BN + ReLU whose input `src` is (WgradArgs::pre): applied on load
 // by the halo 3x3 weight gradient, else the BN output is materialised here first (bigdl_bn_apply)
+// bn_x / bn_coef / bn_aff (all or none): dy is the output gradient of the training BN + ReLU fed by this convolution
+// and the BN's backward apply runs on load (WgradArgs::pre_x); an error unless the pair-view stem kernel takes the call
 void conv_wgrad(const Tensor& dy, const Tensor& src, const Tensor& dw, const OptT& dbias, std::vector<int64_t> geo,
-                const OptT& pre) {
+                const OptT& pre, const OptT& bn_x, const OptT& bn_coef, const OptT& bn_aff) {
   TORCH_CHECK(geo.size() == 18, "conv_wgrad: bad geometry");
-  WgradArgs a;
+  WgradArgs a{};
   a.dy = cbf(dy, "dy"); a.src = cbf(src, "src"); a.dw = mf(dw, "dw"); a.dbias = omf(dbias, "dbias");
   int* f = &a.Nb;
   for (int i = 0; i < 18; ++i) f[i] = (int)geo[i];
@@ -227,6 +229,19 @@ void conv_wgrad(const Tensor& dy, const Tensor& src, const Tensor& dw, const Opt
   a.ws = nullptr;
   a.splits = 0;
   a.pre = ocf(pre, "pre");
+  const bool bnpre = bn_x && bn_x->defined();
+  if (bnpre) {
+    TORCH_CHECK(!a.pre && bn_coef && bn_coef->defined() && bn_aff && bn_aff->defined(),
+                "conv_wgrad: bn_x comes with bn_coef and bn_aff and without pre");
+    TORCH_CHECK(bn_x->numel() == dy.numel() && bn_x->strides() == dy.strides() && a.ldy == a.Ncol,
+                "conv_wgrad: bn_x must have dy's shape and layout");
+    TORCH_CHECK(bn_coef->numel() >= 3 * a.Ncol && bn_coef->is_contiguous() && bn_aff->numel() >= 2 * a.Ncol &&
+                    bn_aff->is_contiguous(),
+                "conv_wgrad: bn_coef is [3 Ncol], bn_aff is [2 Ncol]");
+    a.pre_x = cbf(*bn_x, "bn_x");
+    a.pre_coef = cf(*bn_coef, "bn_coef");
+    a.pre_aff = cf(*bn_aff, "bn_aff");
+  }
   Tensor det_ws;
   a.det_ws = nullptr;
   if (bigdl_deterministic() && a.dbias) {
@@ -255,6 +270,7 @@ void conv_wgrad(const Tensor& dy, const Tensor& src, const Tensor& dw, const Opt
     a.ws = ws.data_ptr<float>();
   }
   const int rc = bigdl_conv_wgrad(&a, stream());
+  TORCH_CHECK(rc != -7, "conv_wgrad: a BN backward on load needs the pair-view stem kernel");
   TORCH_CHECK(rc == 0, "conv_wgrad: unsupported shape (channels must be a multiple of 8)");
 }
 
@@ -310,10 +326,19 @@ void bn_slot_reduce(const Tensor& in, int64_t nslots, int64_t C, const Tensor& o
   bigdl_bn_slot_reduce(cf(in, "in"), (int)nslots, (int)C, mf(out, "out"), stream());
 }
 void bn_apply(const Tensor& x, const Tensor& scale, const Tensor& shift, const OptT& res, const Tensor& y, int64_t P,
-              int64_t C, bool relu, const OptT& zm) {
+              int64_t C, bool relu, const OptT& zm, const OptT& res_scale, const OptT& res_shift) {
   TORCH_CHECK(C % 8 == 0 && x.numel() == P * C && y.numel() == P * C, "bn_apply: shape");
+  const bool ra = res_scale && res_scale->defined();
+  TORCH_CHECK(ra == (res_shift && res_shift->defined()), "bn_apply: res_scale and res_shift come together");
+  if (ra) {
+    TORCH_CHECK(res && res->defined() && res->numel() == P * C, "bn_apply: the residual affine needs a residual");
+    TORCH_CHECK(res_scale->numel() >= C && res_shift->numel() >= C && res_scale->is_contiguous() &&
+                    res_shift->is_contiguous(),
+                "bn_apply: res_scale / res_shift are [C]");
+  }
   bigdl_bn_apply(cbf(x, "x"), cf(scale, "scale"), cf(shift, "shift"), ocbf(res, "res"), mbf(y, "y"), P, (int)C,
-                 relu ? 1 : 0, stream(), omzm(zm, P, C, "zm"));
+                 relu ? 1 : 0, stream(), omzm(zm, P, C, "zm"), ocf(res_scale, "res_scale"),
+                 ocf(res_shift, "res_shift"));
 }
 void bn_bwd_reduce(const Tensor& dz, const OptT& z, const Tensor& x, const Tensor& mean, const Tensor& red, int64_t P,
                    int64_t C, const OptT& aff, const OptT& zm) {
@@ -330,8 +355,7 @@ void bn_bwd_apply(const Tensor& dz, const OptT& z, const Tensor& x, const Tensor
   TORCH_CHECK(coef.numel() >= 3 * C, "bn_bwd_apply: coef size");
   const bool r2 = red2 && red2->defined();
   if (r2) {
-    TORCH_CHECK(dres && dres->defined() && x2 && x2->defined() && mean2 && mean2->defined(),
-                "bn_bwd_apply: red2 needs dres, x2 and mean2");
+    TORCH_CHECK(x2 && x2->defined() && mean2 && mean2->defined(), "bn_bwd_apply: red2 needs x2 and mean2");
     TORCH_CHECK(x2->numel() == x.numel() && x2->strides() == x.strides(), "bn_bwd_apply: x2 must match x's layout");
     TORCH_CHECK(mean2->numel() >= C && red2->numel() >= (int64_t)BIGDL_STAT_SLOTS * 2 * C, "bn_bwd_apply: mean2 / red2 size");
   }
@@ -1679,12 +1703,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_addend_stride_applies", &conv_addend_stride_applies, py::arg("geo"), py::arg("taps"), py::arg("sh"),
         py::arg("sw"), py::arg("bn") = 0);
   m.def("conv_wgrad", &conv_wgrad, py::arg("dy"), py::arg("src"), py::arg("dw"), py::arg("dbias"), py::arg("geo"),
-        py::arg("pre") = py::none());
+        py::arg("pre") = py::none(), py::arg("bn_x") = py::none(), py::arg("bn_coef") = py::none(),
+        py::arg("bn_aff") = py::none());
   m.def("transpose_krsc", &transpose_krsc);
   m.def("bn_stats", &bn_stats);
   m.def("bn_finalize", &bn_finalize);
   m.def("bn_apply", &bn_apply, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("res"), py::arg("y"),
-        py::arg("P"), py::arg("C"), py::arg("relu"), py::arg("zm") = py::none());
+        py::arg("P"), py::arg("C"), py::arg("relu"), py::arg("zm") = py::none(), py::arg("res_scale") = py::none(),
+        py::arg("res_shift") = py::none());
   m.def("bn_slot_reduce", &bn_slot_reduce);
   m.attr("STAT_SLOTS") = BIGDL_STAT_SLOTS;
   m.def("bn_bwd_reduce", &bn_bwd_reduce, py::arg("dz"), py::arg("z"), py::arg("x"), py::arg("mean"), py::arg("red"),

@@ -76,4 +76,23 @@ __device__ __forceinline__ unsigned bf_to_mask8(const v4u& o) {
   return b;
 }
 
+// One bf16 pair of the BatchNorm input gradient dx = A * dy + B * x + D, dy = dz under the ReLU mask x * S + T > 0 when
+// xmask is set (the forward apply's fp32 expression). Shared by bn_bwd_apply_kernel (batchnorm.hip) and the stem weight
+// gradient that applies the stem BN's backward on load (stem_fwd.hip): both must round alike, so the roundings are
+// spelled out instead of being left to the contraction the compiler happens to choose around each call site: the mask
+// is one fma (as every x * scale + shift of the forward is compiled), dx is two rounded products, their rounded sum,
+// and a rounded add of D (what bn_bwd_apply_kernel has always been compiled to). d0 / d1 come back masked.
+__device__ __forceinline__ unsigned bn_bwd_pair(float& d0, float& d1, float x0, float x1, bool xmask, float A0,
+                                                float A1, float B0, float B1, float D0, float D1, float S0, float S1,
+                                                float T0, float T1) {
+#pragma clang fp contract(off)
+  if (xmask) {
+    if (!(__builtin_fmaf(S0, x0, T0) > 0.f)) d0 = 0.f;
+    if (!(__builtin_fmaf(S1, x1, T1) > 0.f)) d1 = 0.f;
+  }
+  const float r0v = A0 * d0 + B0 * x0 + D0;
+  const float r1v = A1 * d1 + B1 * x1 + D1;
+  return pack2bf(r0v, r1v);
+}
+
 #define HIP_LAUNCH_CHECK() (void)hipGetLastError()

@@ -3371,7 +3371,7 @@ static int conv_wgrad_impl(const WgradArgs* a_in, hipStream_t st);
 // taken out of them and summed by a one-row-block column sum (one atomic per channel); the weight gradient always
 // goes through the workspace partials + fixed-order reduce (no multi-split atomics, see bigdl_conv_wgrad_plan).
 int bigdl_conv_wgrad(const WgradArgs* a_in, hipStream_t st) {
-  if (bigdl_deterministic() && a_in->dbias != nullptr && (a_in->ldy % 8) == 0) {
+  if (bigdl_deterministic() && a_in->dbias != nullptr && (a_in->ldy % 8) == 0 && a_in->pre_x == nullptr) {
     WgradArgs b = *a_in;
     b.dbias = nullptr;
     const int rc = conv_wgrad_impl(&b, st);
@@ -3383,6 +3383,12 @@ int bigdl_conv_wgrad(const WgradArgs* a_in, hipStream_t st) {
 
 static int conv_wgrad_impl(const WgradArgs* a_in, hipStream_t st) {
   WgradArgs a = *a_in;
+  if (a.pre_x) {    // dy formed on load from the consumer BN's backward: the pair-view stem kernel only
+    if (a.pre || a.splits != -1 || a.ws == nullptr || bigdl_stem_wgrad_plan(&a) <= 0) return -7;
+    const int rc = bigdl_stem_wgrad(&a, st);
+    HIP_LAUNCH_CHECK();
+    return rc;
+  }
   if (a.pre) {      // a BN applied on load: the halo kernel only (the binding materialises everything else)
     WgradArgs b = a;
     const int hs = bigdl_wgrad_halo_plan(&b);

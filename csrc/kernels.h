@@ -92,6 +92,13 @@ struct WgradArgs {
   // optional [2 Cs] scale | shift: src is the input of a training BN + ReLU, read as relu(src * scale + shift)
   // (ConvArgs::pre semantics; the halo 3x3 weight gradient only: bigdl_wgrad_pre_applies)
   const float* pre;
+  // optional, all three or none (the pair-view stem kernel only, bigdl_stem_wgrad): dy is the output gradient dz of
+  // the training BN + ReLU that consumes this convolution's output pre_x (bf16, dy's layout), and the convolution's
+  // own output gradient A * mask(dz) + B * pre_x + D is formed on load, rounded as bigdl_bn_bwd_apply rounds it.
+  // pre_coef: [3 Ncol] A | B | D (bigdl_bn_bwd_apply's coef); pre_aff: [2 Ncol] scale | shift, mask = pre_x * scale + shift > 0
+  const uint16_t* pre_x;
+  const float* pre_coef;
+  const float* pre_aff;
 };
 
 extern "C" {
@@ -160,7 +167,10 @@ void bigdl_bn_finalize(const float* stats, int nslots, const float* gamma, const
                        long P, int C, float eps, float momentum, int training, hipStream_t st);
 void bigdl_bn_slot_reduce(const float* in, int nslots, int C, float* out, hipStream_t st);
 void bigdl_bn_apply(const uint16_t* x, const float* scale, const float* shift, const uint16_t* res,
-                    uint16_t* y, long P, int C, int relu, hipStream_t st, uint8_t* zm = nullptr);
+                    uint16_t* y, long P, int C, int relu, hipStream_t st, uint8_t* zm = nullptr,
+                    const float* res_scale = nullptr, const float* res_shift = nullptr);
+// res_scale / res_shift (optional, fp32 [C], both or neither): the residual term is bf16(res * res_scale + res_shift),
+// i.e. res is the input of a ReLU-less BN whose own apply pass is folded into this one (bit-equal to running it)
 // aff (optional, [scale C | shift C] of the forward apply): with z == nullptr the ReLU mask is recomputed from x.
 void bigdl_bn_bwd_reduce(const uint16_t* dz, const uint16_t* z, const uint16_t* x, const float* mean,
                          float* red, long P, int C, const float* aff, hipStream_t st, const uint8_t* zm = nullptr);
@@ -170,7 +180,8 @@ void bigdl_bn_bwd_apply(const uint16_t* dz, const uint16_t* z, const uint16_t* x
                         const float* aff, hipStream_t st, const uint8_t* zm = nullptr,
                         const uint16_t* x2 = nullptr, const float* mean2 = nullptr, float* red2 = nullptr);
 // x2 / mean2 / red2: also accumulate the backward reduction of a second (ReLU-less) BN whose output gradient is dres
-// (input x2, same layout; mean2) into the slotted red2 (requires dres; csrc/batchnorm.hip bn_bwd_apply_kernel R2)
+// (input x2, same layout; mean2) into the slotted red2 (csrc/batchnorm.hip bn_bwd_apply_kernel R2). dres may be null
+// there: the sums are taken over the bf16-rounded masked dz whether or not it is stored.
 // zm: [P][C / 8] sign bytes of the post-ReLU output (bit e of byte (p, g) = channel 8g + e > 0), written by
 // bigdl_bn_apply when non-null and read in place of z by the backward passes (1/16 of z's bytes)
 

@@ -145,16 +145,17 @@ namespace {
 
 constexpr int SWRB = 2, SWPX = SWRB * SOW, SWXROWS = 2 * SWRB + SR - 2;   // 224 pixels, 9 input rows per tile
 
-template <int WQ>
+template <int WQ, bool PRE = false>
 struct StemW {
   static constexpr int XB = SWXROWS * WQ * 16;
   static constexpr int XI = (XB + 7 * 1024 - 1) / (7 * 1024);      // DMA rounds of 7 waves x 1 KiB
   static constexpr int XR = XI * 7 * 1024;
   static constexpr int DB = SWPX * 128;                            // dy tile: 224 pixels x 64 channels
   static constexpr int DI = DB / (7 * 1024);
-  static constexpr int LDS1 = XR + DB;                            // one tile buffer
+  static constexpr int LDS1 = XR + (PRE ? 2 : 1) * DB;            // one tile buffer (PRE: + the BN input tile)
   static constexpr int LDS = 2 * LDS1;
   static_assert(DB % (7 * 1024) == 0, "dy tile must split into DMA rounds");
+  static_assert(DB < 65536, "the BN input tile is addressed through a ds offset field");
   static_assert(LDS <= 160 * 1024, "two tile buffers per workgroup");
 };
 
@@ -168,15 +169,23 @@ __device__ __forceinline__ v8s trd2s(unsigned a0, unsigned a1) {
   return v8s{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
-template <int WQ>
+// PRE (WgradArgs::pre_x): a.dy is the output gradient dz of the training BN + ReLU that follows the stem (the pool
+// backward's result) and the stem's own output gradient is that BN's input gradient dy = A * mask(dz) + B * x + D, which
+// is never written: every tile's DMA also brings the matching rows of the BN input x (same chunk swizzle, right behind
+// the dz tile), and once its own DMAs have landed each lane rewrites the dz chunks it fetched in place, with
+// bn_bwd_apply_kernel's expression and rounding (bn_bwd_pair), before the barrier that makes the tile visible. A chunk's
+// channel group is (lane & 7) ^ dyswz(row) and depends on the DMA round only through its parity, so a lane keeps the
+// coefficients of its two groups in registers.
+template <int WQ, bool PRE>
 __global__ __launch_bounds__(448, 1) void stem_wgrad_kernel(WgradArgs a) {
-  using L = StemW<WQ>;
+  using L = StemW<WQ, PRE>;
   __shared__ __attribute__((aligned(1024))) unsigned char lds[L::LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int r = __builtin_amdgcn_readfirstlane(tid >> 6);          // row tap of this wave (7 waves)
   const int tiles_img = a.OH / SWRB, ntiles = a.Nb * tiles_img;
   const bf16_t* xs = reinterpret_cast<const bf16_t*>(a.src);
   const bf16_t* dys = reinterpret_cast<const bf16_t*>(a.dy);
+  const bf16_t* pxs = reinterpret_cast<const bf16_t*>(a.pre_x);
   const size_t xend = (size_t)a.Nb * a.Hs * WQ * 8, dend = (size_t)a.M * 64;
   const unsigned lb = (unsigned)(uintptr_t)(LDS_PTR(unsigned char))lds;
   // dy DMA: LDS chunk (row, slot) holds source chunk (row, slot ^ dyswz(row)) (conflict-free transposed reads)
@@ -185,6 +194,27 @@ __global__ __launch_bounds__(448, 1) void stem_wgrad_kernel(WgradArgs a) {
   for (int d = 0; d < L::DI; ++d) {
     const int Q = (d * 7 + r) * 64 + lane, row = Q >> 3, sl = Q & 7;
     dsrc[d] = (unsigned)((row * 8 + (sl ^ dyswz(row))) * 16);
+  }
+  // PRE: [parity of the DMA round d][8 channels] of A | B | D (pre_coef) and scale | shift (pre_aff)
+  float cA[2][8], cB[2][8], cD[2][8], cS[2][8], cT[2][8];
+  if constexpr (PRE) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int row = ((k * 7 + r) << 3) + (lane >> 3), c0 = ((lane & 7) ^ dyswz(row)) * 8;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const v4f va = *reinterpret_cast<const v4f*>(a.pre_coef + c0 + 4 * h);
+        const v4f vb = *reinterpret_cast<const v4f*>(a.pre_coef + 64 + c0 + 4 * h);
+        const v4f vd = *reinterpret_cast<const v4f*>(a.pre_coef + 128 + c0 + 4 * h);
+        const v4f vs = *reinterpret_cast<const v4f*>(a.pre_aff + c0 + 4 * h);
+        const v4f vt = *reinterpret_cast<const v4f*>(a.pre_aff + 64 + c0 + 4 * h);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          cA[k][4 * h + e] = va[e]; cB[k][4 * h + e] = vb[e]; cD[k][4 * h + e] = vd[e];
+          cS[k][4 * h + e] = vs[e]; cT[k][4 * h + e] = vt[e];
+        }
+      }
+    }
   }
   // transposed-read lane geometry: g = lane >> 4 (8 pixels of the 32-pixel K-step), q = row of a 4-row block,
   // p = 4-column group
@@ -215,11 +245,46 @@ __global__ __launch_bounds__(448, 1) void stem_wgrad_kernel(WgradArgs a) {
     for (int d = 0; d < L::DI; ++d)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (LDS_PTR(void))(B + L::XR + (d * 7 + r) * 1024), 16,
                                                (int)dsrc[d], 0, 0, 0);
+    if constexpr (PRE) {
+      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(pxs + dofs), (short)0,
+                                                                          (int)((dend - dofs) * 2), 0x00020000);
+#pragma unroll
+      for (int d = 0; d < L::DI; ++d)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rp, (LDS_PTR(void))(B + L::XR + L::DB + (d * 7 + r) * 1024), 16,
+                                                 (int)dsrc[d], 0, 0, 0);
+    }
   };
   int buf = 0;
   if ((int)blockIdx.x < ntiles) issue(blockIdx.x, 0);
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x, buf ^= 1) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (PRE) {
+      // inline asm LDS accesses (as in wgrad_halo.hip: plain loads would make the compiler wait for the DMAs itself):
+      // all reads at once, one wait, branch-free rewrites, and the writes retired before the barrier
+      const unsigned db = lb + (unsigned)(buf * L::LDS1 + L::XR) + (unsigned)((r * 64 + lane) * 16);
+      v4u vd[L::DI], vx[L::DI];
+#pragma unroll
+      for (int d = 0; d < L::DI; ++d)
+        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:%3"
+                     : "=v"(vd[d]), "=v"(vx[d]) : "v"(db + (unsigned)(d * 7 * 1024)), "n"(L::DB) : "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int d = 0; d < L::DI; ++d) asm volatile("" : "+v"(vd[d]), "+v"(vx[d]));
+#pragma unroll
+      for (int d = 0; d < L::DI; ++d) {
+        const int k = d & 1;       // (d * 7 + r) and (k * 7 + r) have the same parity: the same channel group
+        v4u o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float d0 = lo_bf(vd[d][e]), d1 = hi_bf(vd[d][e]);
+          o[e] = bn_bwd_pair(d0, d1, lo_bf(vx[d][e]), hi_bf(vx[d][e]), true, cA[k][2 * e], cA[k][2 * e + 1],
+                             cB[k][2 * e], cB[k][2 * e + 1], cD[k][2 * e], cD[k][2 * e + 1], cS[k][2 * e],
+                             cS[k][2 * e + 1], cT[k][2 * e], cT[k][2 * e + 1]);
+        }
+        asm volatile("ds_write_b128 %0, %1" ::"v"(db + (unsigned)(d * 7 * 1024)), "v"(o) : "memory");
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
     __syncthreads();
     if (t + (int)gridDim.x < ntiles) issue(t + gridDim.x, buf ^ 1);
     const unsigned bb = lb + (unsigned)(buf * L::LDS1);
@@ -314,11 +379,17 @@ long bigdl_stem_wgrad_plan(const WgradArgs* a) {
 }
 
 // dW' (fp32 [64][224], a->dw) += the stem weight gradient, a->dbias += the column sums of dy (wave 0's extra MFMAs
-// against a ones operand); a->ws = the plan's workspace.
+// against a ones operand); a->ws = the plan's workspace. With a->pre_x (and pre_coef [3 x 64] A | B | D, pre_aff
+// [2 x 64] scale | shift) a->dy holds dz and dy is formed on load (stem_wgrad_kernel PRE): only this kernel does that.
 int bigdl_stem_wgrad(const WgradArgs* a, hipStream_t st) {
   const long tiles = (long)a->Nb * (a->OH / SWRB);
   const int grid = (int)std::min<long>(tiles, stem_wgrad_grid());
-  stem_wgrad_kernel<115><<<dim3(grid), dim3(448), 0, st>>>(*a);
+  if (a->pre_x) {
+    if (!a->pre_coef || !a->pre_aff) return -7;
+    stem_wgrad_kernel<115, true><<<dim3(grid), dim3(448), 0, st>>>(*a);
+  } else {
+    stem_wgrad_kernel<115, false><<<dim3(grid), dim3(448), 0, st>>>(*a);
+  }
   bigdl_split_reduce_f32(a->ws, a->dw, 64 * 224, grid, st);
   if (a->dbias) bigdl_split_reduce_f32(a->ws + (size_t)grid * 64 * 224, a->dbias, 64, grid, st);
   return 0;
