@@ -36,8 +36,43 @@ uint8_t* omzm(const OptT& t, int64_t P, int64_t C, const char* n) {
   return (uint8_t*)t->data_ptr();
 }
 
-// geo = [Nb, Hs, Ws, Cs, OH, OW, mul_h, mul_w, ldw, Ncol, ldo, OHo, OWo, omul_h, omul_w, ooff_h, ooff_w]
+// geo = [Nb, Hs, Ws, Cs, OH, OW, mul_h, mul_w, ldw, Ncol, ldo, OHo, OWo, omul_h, omul_w, ooff_h, ooff_w (, pstride)]
 // taps = flat [tap_h0, tap_w0, tap_k0, tap_h1, ...]
+void conv_geometry(ConvArgs& a, const std::vector<int64_t>& geo, const std::vector<int64_t>& taps) {
+  a.Nb = geo[0]; a.Hs = geo[1]; a.Ws = geo[2]; a.Cs = geo[3]; a.OH = geo[4]; a.OW = geo[5];
+  a.mul_h = geo[6]; a.mul_w = geo[7]; a.ldw = geo[8]; a.Ncol = geo[9]; a.ldo = geo[10];
+  a.OHo = geo[11]; a.OWo = geo[12]; a.omul_h = geo[13]; a.omul_w = geo[14]; a.ooff_h = geo[15]; a.ooff_w = geo[16];
+  a.pstride = geo.size() == 18 ? (int)geo[17] : 0;
+  a.ntaps = (int)(taps.size() / 3);
+  a.Kdim = a.ntaps * a.Cs;
+  a.M = a.Nb * a.OH * a.OW;
+  a.ident_out = (a.OHo == a.OH && a.OWo == a.OW && a.omul_h == 1 && a.omul_w == 1 && a.ooff_h == 0 && a.ooff_w == 0);
+  for (int t = 0; t < a.ntaps; ++t) {
+    a.tap_h[t] = (short)taps[3 * t]; a.tap_w[t] = (short)taps[3 * t + 1]; a.tap_k[t] = (short)taps[3 * t + 2];
+  }
+  bigdl_conv_addend_stride(&a, 1, 1, 0, 0);
+}
+
+// ConvArgs of a call without tensors, for the planning queries below: bigdl_conv_nt_choose tests pointers for null /
+// alignment only, so present operands are stood in for by an aligned non-null address. bn: 0 = no consumer-BN
+// reduction, 1 = with a sign-mask or affine ReLU mask, 2 = with a bf16 z mask.
+bool conv_stand_in(ConvArgs& a, const std::vector<int64_t>& geo, const std::vector<int64_t>& taps, bool addend,
+                   int64_t bn) {
+  if ((geo.size() != 17 && geo.size() != 18) || taps.size() % 3 != 0 || taps.empty() ||
+      taps.size() / 3 > CONV_MAX_TAPS)
+    return false;
+  a = ConvArgs{};
+  uint16_t* present = reinterpret_cast<uint16_t*>(uintptr_t(256));
+  a.src = present; a.wt = present; a.out = present;
+  if (addend) a.addend = present;
+  if (bn) {
+    a.bnx = present; a.bnmean = reinterpret_cast<const float*>(present); a.bnred = reinterpret_cast<float*>(present);
+    if (bn == 2) a.bnz = present;
+  }
+  conv_geometry(a, geo, taps);
+  return true;
+}
+
 // pre: optional [2 Cs] fp32 scale | shift of a training BN + ReLU whose input `src` is (ConvArgs::pre). When no kernel
 // applies it on load, the BN output is materialised here (bigdl_bn_apply) and returned so the caller can reuse it (the
 // weight gradient reads it); otherwise returns None.
@@ -81,26 +116,16 @@ OptT conv_nt(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
     TORCH_CHECK(bn_mean->numel() >= geo[9] && (!a.bnaff || bn_aff->numel() >= 2 * geo[9]), "conv_nt: bn vectors");
     TORCH_CHECK(bn_red->numel() >= BIGDL_STAT_SLOTS * 2 * geo[9], "conv_nt: bn_red must hold STAT_SLOTS x 2Ncol");
   }
-  a.Nb = geo[0]; a.Hs = geo[1]; a.Ws = geo[2]; a.Cs = geo[3]; a.OH = geo[4]; a.OW = geo[5];
-  a.mul_h = geo[6]; a.mul_w = geo[7]; a.ldw = geo[8]; a.Ncol = geo[9]; a.ldo = geo[10];
-  a.OHo = geo[11]; a.OWo = geo[12]; a.omul_h = geo[13]; a.omul_w = geo[14]; a.ooff_h = geo[15]; a.ooff_w = geo[16];
-  a.pstride = geo.size() == 18 ? (int)geo[17] : 0;
+  conv_geometry(a, geo, taps);
   TORCH_CHECK(a.pstride >= 0 && a.pstride % 8 == 0, "conv_nt: pixel stride must be a multiple of 8");
   a.pre = ocf(pre, "pre");
   if (a.pre)
     TORCH_CHECK(pre->numel() >= 2 * geo[3] && a.pstride == 0 && src.numel() % geo[3] == 0 &&
                     (src.is_contiguous() || src.is_contiguous(at::MemoryFormat::ChannelsLast)),
                 "conv_nt: pre must hold 2 x Cs floats for a dense source");
-  a.ntaps = (int)(taps.size() / 3);
-  a.Kdim = a.ntaps * a.Cs;
-  a.M = a.Nb * a.OH * a.OW;
-  a.ident_out = (a.OHo == a.OH && a.OWo == a.OW && a.omul_h == 1 && a.omul_w == 1 && a.ooff_h == 0 && a.ooff_w == 0);
   a.relu = relu ? 1 : 0;
   int max_tk = 0;
-  for (int t = 0; t < a.ntaps; ++t) {
-    a.tap_h[t] = (short)taps[3 * t]; a.tap_w[t] = (short)taps[3 * t + 1]; a.tap_k[t] = (short)taps[3 * t + 2];
-    max_tk = std::max(max_tk, (int)a.tap_k[t]);
-  }
+  for (int t = 0; t < a.ntaps; ++t) max_tk = std::max(max_tk, (int)a.tap_k[t]);
   if (a.pstride > 0) {   // overlapping windows: every window must end inside its source row
     int max_tw = 0;
     for (int t = 0; t < a.ntaps; ++t) max_tw = std::max(max_tw, (int)a.tap_w[t]);
@@ -116,7 +141,6 @@ OptT conv_nt(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
   TORCH_CHECK(a.ldo >= a.Ncol && out_avail >= ((int64_t)a.Nb * a.OHo * a.OWo - 1) * a.ldo + a.Ncol,
               "conv_nt: out too small");
   if (a.addend) TORCH_CHECK(a.ldo == a.Ncol, "conv_nt: an addend needs a dense output (ldo == Ncol)");
-  bigdl_conv_addend_stride(&a, 1, 1, 0, 0);
   if (asub) {
     // subsampled addend (ConvArgs::add_sh): (Nb, Ncol, ceil(OH / sh), ceil(OW / sw)) channels_last. The caller asks
     // conv_addend_stride_applies first and materialises the addend itself when no kernel takes it
@@ -124,27 +148,28 @@ OptT conv_nt(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
                     addend->size(0) == a.Nb && addend->size(1) == a.Ncol, "conv_nt: subsampled addend must be NHWC");
     bigdl_conv_addend_stride(&a, (int)addend_stride[0], (int)addend_stride[1], (int)addend->size(2),
                              (int)addend->size(3));
-    TORCH_CHECK(bigdl_conv_addend_stride_applies(&a), "conv_nt: no kernel takes this subsampled addend");
   }
   TORCH_CHECK((a.OH - 1) * a.omul_h + a.ooff_h < a.OHo && (a.OW - 1) * a.omul_w + a.ooff_w < a.OWo,
               "conv_nt: output placement out of range");
+  a.ws = nullptr; a.ksplit = 0;
+  ConvChoice choice = bigdl_conv_nt_choose(&a);
+  TORCH_CHECK(choice.kernel != CONV_ERR_ADDEND, "conv_nt: no kernel takes this subsampled addend");
   OptT materialised;
-  if (a.pre && !bigdl_conv_pre_applies(&a)) {
+  if (choice.kernel == CONV_ERR_PRE) {     // no kernel applies the BN on load here
     Tensor y = at::empty_like(src);
     const int64_t P = src.numel() / a.Cs;
     bigdl_bn_apply(a.src, a.pre, a.pre + a.Cs, nullptr, (uint16_t*)y.data_ptr(), P, a.Cs, 1, stream(), nullptr);
     a.src = (const uint16_t*)y.data_ptr();
     a.pre = nullptr;
     materialised = y;
+    choice = bigdl_conv_nt_choose(&a);
   }
-  a.ws = nullptr;
   Tensor ws;
-  const long wsn = bigdl_conv_nt_plan(&a);
-  if (wsn > 0) {     // split-K partials in a caching-allocator workspace (graph-capture safe)
-    ws = at::empty({wsn}, out.options().dtype(at::kFloat));
+  if (choice.ws_floats > 0) {     // split-K partials in a caching-allocator workspace (graph-capture safe)
+    ws = at::empty({choice.ws_floats}, out.options().dtype(at::kFloat));
     a.ws = ws.data_ptr<float>();
   }
-  const int rc = bigdl_conv_nt(&a, stream());
+  const int rc = bigdl_conv_nt(&a, &choice, stream());
   TORCH_CHECK(rc == 0, "conv_nt: unsupported shape (channels must be a multiple of 8; fp32 output needs Ncol % 8 "
               "== 0 and no fused stats / BN / ReLU / addend)");
   return materialised;
@@ -184,33 +209,38 @@ bool dgrad_s2(const Tensor& dy, const Tensor& wt, const Tensor& out, const OptT&
   return true;
 }
 
-// Would conv_nt take an addend subsampled by (sh, sw) for this geometry (conv_nt's geo / taps)? bn: 0 = no consumer-BN
-// reduction, 1 = with a sign-mask or affine ReLU mask, 2 = with a bf16 z mask. No tensors: the native predicate tests
-// pointers for null / alignment only, so present operands are stood in for by an aligned non-null address.
+// Would conv_nt take an addend subsampled by (sh, sw) for this geometry (conv_nt's geo / taps)? bn as conv_stand_in's.
 bool conv_addend_stride_applies(std::vector<int64_t> geo, std::vector<int64_t> taps, int64_t sh, int64_t sw,
                                 int64_t bn) {
-  if (geo.size() != 17 || taps.size() % 3 != 0 || taps.empty() || taps.size() / 3 > CONV_MAX_TAPS) return false;
-  ConvArgs a{};
-  const uint16_t* present = reinterpret_cast<const uint16_t*>(uintptr_t(256));
-  a.src = present; a.wt = present; a.out = const_cast<uint16_t*>(present); a.addend = present;
-  if (bn) {
-    a.bnx = present; a.bnmean = reinterpret_cast<const float*>(present);
-    a.bnred = reinterpret_cast<float*>(const_cast<uint16_t*>(present));
-    if (bn == 2) a.bnz = present;
-  }
-  a.Nb = geo[0]; a.Hs = geo[1]; a.Ws = geo[2]; a.Cs = geo[3]; a.OH = geo[4]; a.OW = geo[5];
-  a.mul_h = geo[6]; a.mul_w = geo[7]; a.ldw = geo[8]; a.Ncol = geo[9]; a.ldo = geo[10];
-  a.OHo = geo[11]; a.OWo = geo[12]; a.omul_h = geo[13]; a.omul_w = geo[14]; a.ooff_h = geo[15]; a.ooff_w = geo[16];
-  a.ntaps = (int)(taps.size() / 3);
-  a.Kdim = a.ntaps * a.Cs;
-  a.M = a.Nb * a.OH * a.OW;
-  a.ident_out = (a.OHo == a.OH && a.OWo == a.OW && a.omul_h == 1 && a.omul_w == 1 && a.ooff_h == 0 && a.ooff_w == 0);
-  for (int t = 0; t < a.ntaps; ++t) {
-    a.tap_h[t] = (short)taps[3 * t]; a.tap_w[t] = (short)taps[3 * t + 1]; a.tap_k[t] = (short)taps[3 * t + 2];
-  }
+  ConvArgs a;
+  if (geo.size() != 17 || !conv_stand_in(a, geo, taps, true, bn)) return false;
   if (sh < 2 || sw < 2 || a.OH < 1 || a.OW < 1) return false;
   bigdl_conv_addend_stride(&a, (int)sh, (int)sw, (int)((a.OH + sh - 1) / sh), (int)((a.OW + sw - 1) / sw));
   return bigdl_conv_addend_stride_applies(&a) != 0;
+}
+
+// What conv_nt would run for this geometry (conv_nt's geo / taps): (kernel name, BM, BN, stages, ksplit, workspace
+// floats); a stream-K choice reports its slots per tile as ksplit. flags: 1 bias, 2 statistics, 4 addend, 8 ReLU,
+// 16 / 32 consumer-BN reduction (conv_stand_in's bn 1 / 2), 64 BN on load (pre), 128 fp32 output; addend_stride =
+// (sh, sw) of a subsampled addend. Touches no GPU memory; tests use it to check which kernel a case reaches.
+py::tuple conv_nt_plan_info(std::vector<int64_t> geo, std::vector<int64_t> taps, int64_t flags,
+                            std::vector<int64_t> addend_stride) {
+  ConvArgs a;
+  TORCH_CHECK(conv_stand_in(a, geo, taps, (flags & 4) != 0, (flags & 32) ? 2 : (flags & 16) ? 1 : 0),
+              "conv_nt_plan_info: bad geometry");
+  float* presentf = reinterpret_cast<float*>(uintptr_t(256));
+  if (flags & 1) a.bias = presentf;
+  if (flags & 2) a.stats = presentf;
+  if (flags & 8) a.relu = 1;
+  if (flags & 64) a.pre = presentf;
+  if (flags & 128) { a.out32 = presentf; a.out = nullptr; }
+  if (addend_stride.size() == 2)
+    bigdl_conv_addend_stride(&a, (int)addend_stride[0], (int)addend_stride[1],
+                             (int)((a.OH + addend_stride[0] - 1) / addend_stride[0]),
+                             (int)((a.OW + addend_stride[1] - 1) / addend_stride[1]));
+  const ConvChoice c = bigdl_conv_nt_choose(&a);
+  return py::make_tuple(bigdl_conv_kernel_name(c.kernel), c.BM, c.BN, c.stages,
+                        c.kernel == CONV_P8_SK ? c.sk_slots : c.ksplit, (int64_t)c.ws_floats);
 }
 
 // geo = [Nb, Hs, Ws, Cs, OH, OW, R, S, sh, sw, ph, pw, dh, dw, M, Ncol, Kdim, ldy]
@@ -264,43 +294,42 @@ void conv_wgrad(const Tensor& dy, const Tensor& src, const Tensor& dw, const Opt
   TORCH_CHECK(dy.numel() >= (int64_t)(a.M - 1) * a.ldy + a.Ncol, "conv_wgrad: dy too small");
   TORCH_CHECK(src.numel() >= (int64_t)a.Nb * a.Hs * a.Ws * a.Cs, "conv_wgrad: src too small");
   Tensor ws;
-  const long wsn = bigdl_conv_wgrad_plan(&a);
-  if (wsn > 0) {     // split-K partials in a caching-allocator workspace (graph-capture safe)
-    ws = at::empty({wsn}, dw.options().dtype(at::kFloat));
+  const WgradChoice choice = bigdl_conv_wgrad_choose(&a);
+  if (choice.ws_floats > 0) {     // split-K partials in a caching-allocator workspace (graph-capture safe)
+    ws = at::empty({choice.ws_floats}, dw.options().dtype(at::kFloat));
     a.ws = ws.data_ptr<float>();
   }
-  const int rc = bigdl_conv_wgrad(&a, stream());
-  TORCH_CHECK(rc != -7, "conv_wgrad: a BN backward on load needs the pair-view stem kernel");
+  const int rc = bigdl_conv_wgrad(&a, &choice, stream());
+  TORCH_CHECK(rc != WGRAD_ERR_PRE_X, "conv_wgrad: a BN backward on load needs the pair-view stem kernel");
   TORCH_CHECK(rc == 0, "conv_wgrad: unsupported shape (channels must be a multiple of 8)");
+}
+
+WgradChoice wgrad_choice_of(const std::vector<int64_t>& geo, bool bias, const char* who) {
+  TORCH_CHECK(geo.size() == 18, who, ": bad geometry");
+  WgradArgs a{};
+  int* f = &a.Nb;
+  for (int i = 0; i < 18; ++i) f[i] = (int)geo[i];
+  static float dummy;
+  a.dbias = bias ? &dummy : nullptr;
+  return bigdl_conv_wgrad_choose(&a);
 }
 
 // true when conv_wgrad would run the phase-interleaved 256 x 256 kernel on this geometry (callers skip the
 // transpose-based NT GEMM route then)
 bool conv_wgrad_uses_p8(std::vector<int64_t> geo, bool bias) {
-  TORCH_CHECK(geo.size() == 18, "conv_wgrad_uses_p8: bad geometry");
-  WgradArgs a{};
-  int* f = &a.Nb;
-  for (int i = 0; i < 18; ++i) f[i] = (int)geo[i];
-  static float dummy;
-  a.dbias = bias ? &dummy : nullptr;
-  return bigdl_conv_wgrad_uses_p8(&a) != 0;
+  const int k = wgrad_choice_of(geo, bias, "conv_wgrad_uses_p8").kernel;
+  return k == WGRAD_P8 || k == WGRAD_P8_DIRECT;
 }
 
-// What conv_wgrad would do with this geometry: [splits (-1 = stem pair kernel, 0 = atomic path, which splits by
-// itself), workspace floats, halo-kernel splits (0 = not the halo kernel), 1 if the 256 x 256 kernel takes it, 1 if
-// the register-staged conv_wgrad_kernel takes it]. Tests use it to check which kernel a case reaches.
+// What conv_wgrad would do with this geometry: [splits (-1 = stem pair kernel, 0 = the register-staged atomic kernel,
+// which splits by itself, 1 = no workspace split), workspace floats, halo-kernel splits (0 = not the halo kernel), 1 if
+// the 256 x 256 kernel takes it, 1 if the register-staged conv_wgrad_kernel takes it]. Tests use it to check which
+// kernel a case reaches.
 std::vector<int64_t> conv_wgrad_plan_info(std::vector<int64_t> geo, bool bias) {
-  TORCH_CHECK(geo.size() == 18, "conv_wgrad_plan_info: bad geometry");
-  WgradArgs a{};
-  int* f = &a.Nb;
-  for (int i = 0; i < 18; ++i) f[i] = (int)geo[i];
-  static float dummy;
-  a.dbias = bias ? &dummy : nullptr;
-  WgradArgs h = a, p = a;
-  const int halo = bigdl_wgrad_halo_plan(&h);
-  const int p8 = halo > 0 ? 0 : bigdl_conv_wgrad_uses_p8(&p);
-  const long wsn = bigdl_conv_wgrad_plan(&a);
-  return {a.splits, wsn, halo, p8, bigdl_conv_wgrad_uses_register_kernel(&a)};
+  const WgradChoice c = wgrad_choice_of(geo, bias, "conv_wgrad_plan_info");
+  const bool atomic = c.kernel == WGRAD_GLDS_ATOMIC || c.kernel == WGRAD_G3_ATOMIC;
+  return {c.kernel == WGRAD_REG ? 0 : atomic ? 1 : c.splits, c.ws_floats, c.kernel == WGRAD_HALO ? c.splits : 0,
+          c.kernel == WGRAD_P8 || c.kernel == WGRAD_P8_DIRECT, c.kernel == WGRAD_REG};
 }
 
 void transpose_krsc(const Tensor& w, const Tensor& wt, int64_t K, int64_t RS, int64_t C) {
@@ -1864,9 +1893,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_conv_g4", &bigdl_set_conv_g4);
   m.def("set_conv_shortk", &bigdl_set_conv_shortk);
   m.def("set_conv_p8", &bigdl_set_conv_p8);
+  m.def("set_conv_w8", &bigdl_set_conv_w8);
   m.def("set_wgrad_p8", &bigdl_set_wgrad_p8);
   m.def("conv_wgrad_uses_p8", &conv_wgrad_uses_p8);
   m.def("conv_wgrad_plan_info", &conv_wgrad_plan_info);
+  m.def("conv_nt_plan_info", &conv_nt_plan_info, py::arg("geo"), py::arg("taps"), py::arg("flags") = 0,
+        py::arg("addend_stride") = std::vector<int64_t>());
   m.def("get_conv_g4", &bigdl_get_conv_g4);
   m.def("set_wgrad_g3", &bigdl_set_wgrad_g3);
   m.def("get_wgrad_g3", &bigdl_get_wgrad_g3);

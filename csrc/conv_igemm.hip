@@ -1883,10 +1883,7 @@ __global__ __launch_bounds__(512, 1) void conv_nt_w8_kernel(ConvArgs a) {
 // tail past Kdim loads zeros.
 // BM = 256 (BIGDL_CONV_G4=6/7): 2 x 2 waves of 128 x 64, 32 MFMAs per wave between barriers instead of 16, 24 KB
 // stages, 2 workgroups per CU.
-// ABN = 1: timing ablation (BIGDL_G4_ABN=1 with ConvArgs::pre set; padding taps are not masked, so only 1x1 outputs
-// are right) — the BN scale / shift + ReLU applied to every A fragment after its LDS read, coefficients loaded per
-// K-step (what folding a BN apply into this tile's operand costs; round 4: +1.15 ms on the forward convs).
-template <int BN, int NS, bool FASTK = true, int BM = 128, int ABN = 0>
+template <int BN, int NS, bool FASTK = true, int BM = 128>
 // NS = 2 (short-K variant, BIGDL_CONV_SHORTK): Kdim <= 64, both K-steps issued up front, 32 KB of stages and four
 // workgroups per CU for these one-DMA-round, epilogue-heavy tiles (the caller guarantees nk <= 2).
 __global__ __launch_bounds__(256, NS == 2 ? 4 : ((NS == 3 && BM == 128) ? 3 : 2)) void conv_nt_g4_kernel(ConvArgs a) {
@@ -2015,21 +2012,6 @@ __global__ __launch_bounds__(256, NS == 2 ? 4 : ((NS == 3 && BM == 128) ? 3 : 2)
     for (int j = 0; j < NI; ++j) fb[j] = *reinterpret_cast<const v8s*>(B + (wn * TN + j * 16) * BKS + foff);
 #pragma unroll
     for (int i = 0; i < MI; ++i) fa[i] = *reinterpret_cast<const v8s*>(A + (wm * TM + i * 16) * BKS + foff);
-    if constexpr (ABN) {
-      const int c0 = (kt * BKS) % a.Cs + 8 * (lane >> 4);
-      const v4f s0 = *reinterpret_cast<const v4f*>(a.pre + c0), s1 = *reinterpret_cast<const v4f*>(a.pre + c0 + 4);
-      const v4f t0 = *reinterpret_cast<const v4f*>(a.pre + a.Cs + c0), t1 = *reinterpret_cast<const v4f*>(a.pre + a.Cs + c0 + 4);
-      const float sc[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
-      const float sh[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        v4u u = __builtin_bit_cast(v4u, fa[i]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          u[e] = pack2bf(fmaxf(lo_bf(u[e]) * sc[2 * e] + sh[2 * e], 0.f), fmaxf(hi_bf(u[e]) * sc[2 * e + 1] + sh[2 * e + 1], 0.f));
-        fa[i] = __builtin_bit_cast(v8s, u);
-      }
-    }
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -2070,9 +2052,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 4 : ((NS == 3 && BM == 128) ? 3 : 2)
 // overwritten at least two phases after its last read, by which time both groups retired that read (lgkmcnt(0) at
 // the start of their COMPUTE segment). The wave tile and the epilogue are those of conv_nt_w8_kernel.
 // FASTK only (Cs % 64 == 0: a K-tile lies in one tap). SPLIT: fp32 partials of a K range per blockIdx.y.
-// ABL (diagnostic ablation builds, BIGDL_P8_ABL; wrong outputs): bit 0 no LDS-DMA inside the K-loop, bit 1 no fragment
-// ds_reads after the first K-tile, bit 2 no wave-group stagger, bit 3 no MFMAs, bit 4 no A-operand DMA, bit 5 no
-// B-operand DMA; bit 6 (64) is not an ablation: the one-tap K-tail mode (Cs % 64 != 0, granules past Kdim zero)
+// KTAIL: the one-tap K-tail mode (Cs % 64 != 0: granules past Kdim load zeros).
 // SK (stream-K): gridDim.x persistent workgroups (one per CU) share the tiles x K-tiles iteration space evenly, so a
 // small grid (ResNet-50's 14x14 / 7x7 layers: 98-392 tiles of 256 x 256 on 256 CUs) keeps every CU busy. A workgroup
 // runs its range as segments (one tile's K sub-range each) through the same pipeline; a segment that covers a whole
@@ -2082,7 +2062,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 4 : ((NS == 3 && BM == 128) ? 3 : 2)
 // arrival order: deterministic), and runs the fused epilogue. Nobody waits on anybody: correct whatever the
 // residency (the splitk-seam recipe of cdna_hip_programming.md §5 item 2, last-arriver form). a.ksplit = slots per
 // tile; the tickets follow the slots in ws and are zeroed by a fill kernel before the launch.
-template <bool SPLIT, int ABL = 0, bool SK = false>
+template <bool SPLIT, bool KTAIL = false, bool SK = false>
 __global__ __launch_bounds__(512, 2) void conv_nt_p8_kernel(ConvArgs a) {
   constexpr int BM = 256, BN = 256, BKT = 64;
   constexpr int WGM = 2, WGN = 4;
@@ -2103,7 +2083,6 @@ __global__ __launch_bounds__(512, 2) void conv_nt_p8_kernel(ConvArgs a) {
   const int tiles_n = (a.Ncol + BN - 1) / BN;
   const int tiles_m = (a.M + BM - 1) / BM;
   const int nwg = tiles_m * tiles_n;
-  constexpr bool KTAIL = (ABL & 64) != 0;          // one tap, Cs % 64 != 0: granules past Kdim load zeros
   const int nk_all = KTAIL ? (a.Kdim + BKT - 1) / BKT : a.Kdim / BKT;
   if (tid < a.ntaps) {
     taps[tid] = a.tap_h[tid];
@@ -2179,8 +2158,6 @@ __global__ __launch_bounds__(512, 2) void conv_nt_p8_kernel(ConvArgs a) {
     const int cin = k0 - t * a.Cs;
     bf16_t* base = lds + buf * BUF + P * PIECE;
     const int q = P >> 1;
-    if ((ABL & 16) && (P & 1) == 0) return;
-    if ((ABL & 32) && (P & 1) == 1) return;
     if ((P & 1) == 0) {
       const int th = taps[t], tw = taps[CONV_MAX_TAPS + t];
       const int c = cin + gsrc * 8;
@@ -2247,7 +2224,7 @@ __global__ __launch_bounds__(512, 2) void conv_nt_p8_kernel(ConvArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    if constexpr (!(ABL & 8)) quad(ib, jb);
+    quad(ib, jb);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -2264,35 +2241,35 @@ __global__ __launch_bounds__(512, 2) void conv_nt_p8_kernel(ConvArgs a) {
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   }
   __builtin_amdgcn_s_barrier();
-  if (!(ABL & 4) && wm == 1) __builtin_amdgcn_s_barrier();   // stagger: the second M-half runs one barrier behind
+  if (wm == 1) __builtin_amdgcn_s_barrier();   // stagger: the second M-half runs one barrier behind
 
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     const bf16_t* L = lds + cur * BUF;
     const bool n1 = kt + 1 < nk, n2 = kt + 2 < nk;
     // ---- phase 0
-    if (!(ABL & 1) && n1) issue(kt0 + kt + 1, cur ^ 1, 3);
-    if (!(ABL & 2) || kt == 0) { read_a(L); read_b(L + PIECE, 0); }
+    if (n1) issue(kt0 + kt + 1, cur ^ 1, 3);
+    read_a(L); read_b(L + PIECE, 0);
     if (n1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");          // P3(t) landed
     else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     compute(0, 0);
     // ---- phase 1
-    if (!(ABL & 1) && n1) issue(kt0 + kt + 1, cur ^ 1, 2);
-    if (!(ABL & 2) || kt == 0) read_b(L + 3 * PIECE, 2);
+    if (n1) issue(kt0 + kt + 1, cur ^ 1, 2);
+    read_b(L + 3 * PIECE, 2);
     if (n1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");          // P2(t) landed
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     compute(0, 2);
     // ---- phase 2
-    if (!(ABL & 1) && n2) issue(kt0 + kt + 2, cur, 0);
-    if (!(ABL & 2) || kt == 0) read_a(L + 2 * PIECE);
+    if (n2) issue(kt0 + kt + 2, cur, 0);
+    read_a(L + 2 * PIECE);
     compute(4, 2);
     // ---- phase 3
-    if (!(ABL & 1) && n2) issue(kt0 + kt + 2, cur, 1);
+    if (n2) issue(kt0 + kt + 2, cur, 1);
     if (n2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");          // P0, P1(t+1) landed
     else if (n1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     compute(4, 0);
   }
-  if (!(ABL & 4) && wm == 0) __builtin_amdgcn_s_barrier();   // balance the stagger: every wave has left the K-loop
+  if (wm == 0) __builtin_amdgcn_s_barrier();   // balance the stagger: every wave has left the K-loop
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   float* wl = reinterpret_cast<float*>(lds) + wave * SL;
   if constexpr (SK) {
@@ -2772,6 +2749,106 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(ConvArgs a, l
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dispatch. Every switch lives in one table (ConvSwitches); bigdl_conv_nt_choose / bigdl_conv_wgrad_choose are the
+// only places that decide which kernel runs, and bigdl_conv_nt / bigdl_conv_wgrad only launch what they chose.
+// ------------------------------------------------------------------------------------------------
+struct ConvSwitches {
+  // BIGDL_CONV_IMPL: 3 = persistent LDS-DMA kernel (next tile's loads overlap the epilogue) on grids of more
+  // than two tiles per CU, 2 = deep-pipelined 256-pixel kernel on grids that fill the chip,
+  // 1 (default) = LDS-DMA kernel where Cs % 64 == 0, 0 = register-staged kernel everywhere.
+  int impl;
+  // BIGDL_CONV_ONESTAGE (default 1): single-stage kernel for Kdim == BK (0 disables it for A/B runs)
+  int onestage;
+  // BIGDL_CONV_GLDS_SLOWK (default 1): LDS-DMA path for Cs % 64 != 0 (0 restores the register-staged kernel there)
+  int glds_slowk;
+  // BIGDL_CONV_W8 (default 0): the 256 x 256 8-wave kernel, see w8_pick; 2 = never split along K
+  int w8;
+  // BIGDL_CONV_P8: 0 = off, 1 (default) = the 256 x 256 phase-interleaved kernel on fast-K (Cs % 64 == 0) layers with
+  // Ncol >= 256 and Kdim >= 256, split over K when its grid would leave CUs idle; 2 = wherever it applies (tests).
+  int p8;
+  // BIGDL_CONV_SK: stream-K for the 256 x 256 P8 kernel. 0 (default): off — it measured slower than the plain P8
+  // grid on every ResNet-50 layer its rule selects (profiles/r5_stream_k_ab.txt); 1 = on grids that leave CUs idle (a
+  // plain grid of tiles fills < 85 % of its last dispatch round) with deep reductions (Kdim >= BIGDL_CONV_SK_K, default
+  // 1024); 2 = wherever the P8 kernel applies (tests).
+  int sk, sk_k;
+  // BIGDL_CONV_G4 (default 3): 0 = off, 4 = 4-stage (2 workgroups per CU), 3 = 3-stage (3 per CU) deep-pipelined 128-row kernel
+  // in place of the 2-stage LDS-DMA kernel on fast-K (Cs % 32 == 0), aligned-output layers; 5 = the 3-stage kernel
+  // also on the deep-K small-grid layers that otherwise take the 256-row 8-wave kernel; 6 = as 3, with the 256 x 128 tile
+  // for Ncol > 64 wherever its grid still gives every CU two workgroups; 7 = as 3, with the 256 x 128 tile always
+  // for Ncol > 64 (tests). 3-stage default: ResNet-50 b256 27.35 -> 26.48 ms/step (profiles/r3_conv_g4_ab.txt)
+  int g4;
+  // BIGDL_CONV_G4_SLOWK (default 1): the multi-stage kernel also for Cs % 32 != 0 (per-lane taps)
+  int g4_slowk;
+  // BIGDL_CONV_SHORTK (default 0): the two-stage, 4-workgroups-per-CU variant of the 128 x 64 multi-stage kernel when
+  // Kdim <= 64 and Ncol <= 64. Measured neutral on ResNet-50 b256 training (25.78 / 25.89 vs 25.81 / 25.91 ms,
+  // profiles/r4_shortk_ab.txt)
+  int shortk;
+  // BIGDL_CONV_S1 (default 2): the streaming 1x1 kernel (conv_nt_s1_kernel) wherever it applies, Kdim 64 / 128 / 256;
+  // 1 = Kdim 64 / 128 only (round 5; the 256-deep form runs one workgroup per CU with 128 weight VGPRs per wave:
+  // ResNet-50 22.62 -> 22.31 ms/step interleaved A/B, profiles/r6_iteration_log.txt); 3 = Kdim 256 only without the
+  // extended epilogue (addend / consumer-BN reduction: data gradients stay on the tile kernels); 0 = off (A/B)
+  int s1;
+  // BIGDL_CONV_P3AUTO (default 1): deep-K layers on small pixel grids (ResNet stages 4-5: <= 50k output pixels,
+  // K >= 1024) run faster on the 8-wave deep-pipelined kernel (tools/bench_conv.py, impl 1 vs 2); 0 keeps them on impl 1
+  int p3auto;
+  // BIGDL_WGRAD_ATOMIC: 1 (default) the half-empty-tile rule of wgrad_prefers_atomic, 0 never, 2 always (per-layer
+  // A/B runs); never in deterministic mode
+  int wgrad_atomic;
+  // BIGDL_WGRAD_ATOMIC_MB (default 32): cap of the atomic path's fp32 traffic, splits x |dW| x 4 B
+  int wgrad_atomic_mb;
+  // BIGDL_WGRAD_WGS (default 512): workgroup target of the workspace split (fewer splits = fewer partials to reduce)
+  int wgrad_wgs;
+  // BIGDL_WGRAD_G3=1: the 3-stage counted-vmcnt weight-gradient kernel in place of the 2-stage one
+  int wgrad_g3;
+  // BIGDL_WGRAD_TR_ASM: 1 (default) = the weight-gradient kernels read their fragments with inline-assembly
+  // transposing reads and hand-placed waits (lds_tr.h); 0 = through the compiler intrinsic, which drains the LDS-DMA
+  // in front of every group of reads. Same kernels (a template flag), same results bit for bit; for A/B runs.
+  int wgrad_tr_asm;
+  // BIGDL_WGRAD_P8: 1 (default) = conv_wgrad_p8_kernel where it measured faster (p8w_pick), 2 = on every layer with
+  // Ncol >= 256 and Kdim >= 256 (tests / A/B), 0 = off.
+  int wgrad_p8;
+};
+
+ConvSwitches& sw() {
+  static ConvSwitches s = [] {
+    auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    ConvSwitches t;
+    t.impl = env("BIGDL_CONV_IMPL", 1);
+    t.onestage = env("BIGDL_CONV_ONESTAGE", 1);
+    t.glds_slowk = env("BIGDL_CONV_GLDS_SLOWK", 1);
+    t.w8 = env("BIGDL_CONV_W8", 0);
+    t.p8 = env("BIGDL_CONV_P8", 1);
+    t.sk = env("BIGDL_CONV_SK", 0);
+    t.sk_k = env("BIGDL_CONV_SK_K", 1024);
+    t.g4 = env("BIGDL_CONV_G4", 3);
+    t.g4_slowk = env("BIGDL_CONV_G4_SLOWK", 1);
+    t.shortk = env("BIGDL_CONV_SHORTK", 0);
+    t.s1 = env("BIGDL_CONV_S1", 2);
+    t.p3auto = env("BIGDL_CONV_P3AUTO", 1);
+    t.wgrad_atomic = env("BIGDL_WGRAD_ATOMIC", 1);
+    t.wgrad_atomic_mb = env("BIGDL_WGRAD_ATOMIC_MB", 32);
+    t.wgrad_wgs = env("BIGDL_WGRAD_WGS", 512);
+    t.wgrad_g3 = env("BIGDL_WGRAD_G3", 0);
+    t.wgrad_tr_asm = env("BIGDL_WGRAD_TR_ASM", 1);
+    t.wgrad_p8 = env("BIGDL_WGRAD_P8", 1);
+    return t;
+  }();
+  return s;
+}
+
+// compute units of the current device, read once
+int conv_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (cus <= 0) cus = 256;
+  }
+  return cus;
+}
+
 template <int BM, int BN, int WM>
 void launch_nt(const ConvArgs& a, bool fastk, hipStream_t st) {
   const int nwg = ((a.M + BM - 1) / BM) * ((a.Ncol + BN - 1) / BN);
@@ -2784,18 +2861,6 @@ template <int BM, int BN, int WM, bool FASTK = true, int NST = 2>
 void launch_nt_glds(const ConvArgs& a, hipStream_t st) {
   const int nwg = ((a.M + BM - 1) / BM) * ((a.Ncol + BN - 1) / BN);
   conv_nt_glds_kernel<BM, BN, WM, FASTK, NST><<<dim3(nwg), dim3(256), 0, st>>>(a);
-}
-
-// single-stage kernel for Kdim == BK (BIGDL_CONV_ONESTAGE=0 disables it for A/B runs)
-static bool conv_onestage() {
-  static int v = [] { const char* e = getenv("BIGDL_CONV_ONESTAGE"); return e ? atoi(e) : 1; }();
-  return v != 0;
-}
-
-// LDS-DMA path for Cs % 64 != 0 (BIGDL_CONV_GLDS_SLOWK=0 restores the register-staged kernel there)
-static bool glds_slowk() {
-  static int v = [] { const char* e = getenv("BIGDL_CONV_GLDS_SLOWK"); return e ? atoi(e) : 1; }();
-  return v != 0;
 }
 
 template <int BM, int BN, int WM>
@@ -2811,169 +2876,19 @@ void launch_nt_p3(const ConvArgs& a, hipStream_t st) {
   conv_nt_p3_kernel<BN, WGM, WGN><<<dim3(nwg), dim3(512), 0, st>>>(a);
 }
 
-// BIGDL_CONV_IMPL: 3 = persistent LDS-DMA kernel (next tile's loads overlap the epilogue) on grids of more
-// than two tiles per CU, 2 = deep-pipelined 256-pixel kernel on grids that fill the chip,
-// 1 (default) = LDS-DMA kernel where Cs % 64 == 0, 0 = register-staged kernel everywhere.
-// 256 x 256 8-wave kernel (BIGDL_CONV_W8=0 disables it): fast-K over 32-channel steps, aligned bf16 output, at
-// least 256 output channels, at least 4 K-steps of 32. Returns 0 (not picked) or the K split (1 = none): grids below
-// one workgroup per CU are split along K (>= 8 K-steps per split) so every CU gets work.
-static int w8_pick(const ConvArgs* a) {
-  static const int on = [] { const char* e = getenv("BIGDL_CONV_W8"); return e ? atoi(e) : 0; }();
-  if (!on || a->out32 || (a->Cs % 32) || (a->Ncol & 7) || (a->ldo & 7) || a->Ncol < 256 || a->Kdim < 128) return 0;
-  const long tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-  const int nk = a->Kdim / 32;
-  if (tiles >= 200 || on == 2) return 1;
-  int split = (int)((320 + tiles - 1) / tiles);
-  split = std::min(split, std::max(1, nk / 8));
-  split = std::min(split, 8);
-  return std::max(split, 1);
-}
-
-// BIGDL_CONV_P8: 0 = off, 1 (default) = the 256 x 256 phase-interleaved kernel on fast-K (Cs % 64 == 0) layers with
-// Ncol >= 256 and Kdim >= 256, split over K when its grid would leave CUs idle; 2 = wherever it applies (tests).
-// Returns 0 (not used), 1 (one pass) or the K split.
-int g_conv_p8 = -1;
-static int p8_pick(const ConvArgs* a) {
-  if (g_conv_p8 < 0) {
-    const char* e = getenv("BIGDL_CONV_P8");
-    g_conv_p8 = e ? atoi(e) : 1;
-  }
-  const int on = g_conv_p8;
-  const bool ktail = (a->Cs % 64) != 0 && a->ntaps == 1 && a->Cs % 8 == 0 && a->Kdim == a->Cs;   // p8_ktail()
-  if (!on || a->out32 || ((a->Cs % 64) && !ktail) || (a->Ncol & 7) || (a->ldo & 7) || a->Kdim < 128) return 0;
-  // auto: deep reductions only. Per layer (tools/conv_roofline.py, ResNet-50 b256) the one-workgroup-per-CU tile wins
-  // from K = 1024 up (3x3 over 256 channels 101 -> 86 us) and loses below, where its prologue / epilogue are not
-  // hidden by a co-resident workgroup (1x1 512 -> 1024 stride 2: 103 -> 147 us)
-  if (on == 1 && (a->Ncol < 256 || a->Kdim < 1024)) return 0;
-  const long tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-  const int nk = a->Kdim / 64;
-  if (tiles >= 160) return 1;
-  // split-K measured slower than the 256 x 128 deep-K kernel on the small ResNet grids (12544 x 512, K 4608:
-  // 452 vs 544 TF/s, tools/gemm_ceiling.py): auto mode leaves grids under 160 tiles to the other kernels
-  if (on == 1) return 0;
-  int split = (int)((256 + tiles - 1) / tiles);
-  split = std::min(split, std::max(1, nk / 4));
-  split = std::min(split, 8);
-  return std::max(split, 1);
-}
-
-// BIGDL_CONV_SK: stream-K for the 256 x 256 P8 kernel. 0 (default): off — it measured slower than the plain P8
-// grid on every ResNet-50 layer its rule selects (profiles/r5_stream_k_ab.txt); 1 = on grids that leave CUs idle (a
-// plain grid of tiles fills < 85 % of its last dispatch round) with deep reductions (Kdim >= BIGDL_CONV_SK_K, default
-// 1024); 2 = wherever the P8 kernel applies (tests). Returns the (tile, segment) slots per tile, 0 when not used.
-int g_conv_sk = -1;
-int conv_impl();
-static int sk_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-static int sk_pick(const ConvArgs* a) {
-  if (g_conv_sk < 0) {
-    const char* e = getenv("BIGDL_CONV_SK");
-    g_conv_sk = e ? atoi(e) : 0;
-  }
-  static const int kmin = [] { const char* e = getenv("BIGDL_CONV_SK_K"); return e ? atoi(e) : 1024; }();
-  if (!g_conv_sk || conv_impl() != 1 || a->out32 || (a->Cs % 64) || (a->Ncol & 7) || (a->ldo & 7)) return 0;
-  if (g_conv_p8 == 0) return 0;
-  if (g_conv_sk == 1 && (a->Ncol < 256 || a->Kdim < kmin)) return 0;
-  const long tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-  const int G = sk_cus();
-  const int nk = a->Kdim / 64;
-  const double eff = (double)tiles / (double)(((tiles + G - 1) / G) * G);
-  if (g_conv_sk == 1 && eff >= 0.85) return 0;
-  const long q = (tiles * nk) / G;
-  if (q < 4) return 0;                      // ranges too short for the pipeline
-  return (int)(nk / q + 2);
-}
-
 template <int BN, int NS, int BM = 128>
 void launch_nt_g4(const ConvArgs& a, hipStream_t st) {
   const int nwg = ((a.M + BM - 1) / BM) * ((a.Ncol + BN - 1) / BN);
-  static const int abn = [] { const char* e = getenv("BIGDL_G4_ABN"); return e ? atoi(e) : 0; }();
-  if (abn && a.pre && BM == 128 && NS == 3 && a.Cs % 32 == 0)
-    conv_nt_g4_kernel<BN, NS, true, BM, 1><<<dim3(nwg), dim3(256), 0, st>>>(a);
-  else if (a.Cs % 32 == 0) conv_nt_g4_kernel<BN, NS, true, BM><<<dim3(nwg), dim3(256), 0, st>>>(a);
+  if (a.Cs % 32 == 0) conv_nt_g4_kernel<BN, NS, true, BM><<<dim3(nwg), dim3(256), 0, st>>>(a);
   else conv_nt_g4_kernel<BN, NS, false, BM><<<dim3(nwg), dim3(256), 0, st>>>(a);
-}
-
-// BIGDL_CONV_G4 (default 3): 0 = off, 4 = 4-stage (2 workgroups per CU), 3 = 3-stage (3 per CU) deep-pipelined 128-row kernel
-// in place of the 2-stage LDS-DMA kernel on fast-K (Cs % 32 == 0), aligned-output layers; 5 = the 3-stage kernel
-// also on the deep-K small-grid layers that otherwise take the 256-row 8-wave kernel; 6 = as 3, with the 256 x 128 tile
-// for Ncol > 64 wherever its grid still gives every CU two workgroups; 7 = as 3, with the 256 x 128 tile always
-// for Ncol > 64 (tests)
-int g_conv_g4 = -1;
-static int g4_pick() {
-  if (g_conv_g4 < 0) {
-    const char* e = getenv("BIGDL_CONV_G4");
-    g_conv_g4 = e ? atoi(e) : 3;   // 3-stage default: ResNet-50 b256 27.35 -> 26.48 ms/step (profiles/r3_conv_g4_ab.txt)
-  }
-  return g_conv_g4;
-}
-
-// BIGDL_CONV_G4_SLOWK (default 1): the multi-stage kernel also for Cs % 32 != 0 (per-lane taps)
-static bool g4_slowk() {
-  static const int v = [] { const char* e = getenv("BIGDL_CONV_G4_SLOWK"); return e ? atoi(e) : 1; }();
-  return v != 0;
-}
-
-// BIGDL_CONV_SHORTK (default 0): the two-stage, 4-workgroups-per-CU variant of the 128 x 64 multi-stage kernel when
-// Kdim <= 64 and Ncol <= 64. Measured neutral on ResNet-50 b256 training (25.78 / 25.89 vs 25.81 / 25.91 ms,
-// profiles/r4_shortk_ab.txt)
-int g_conv_shortk = -1;
-static bool conv_shortk() {
-  if (g_conv_shortk < 0) {
-    const char* e = getenv("BIGDL_CONV_SHORTK");
-    g_conv_shortk = e ? atoi(e) : 0;
-  }
-  return g_conv_shortk != 0;
-}
-
-// BIGDL_CONV_S1 (default 2): the streaming 1x1 kernel (conv_nt_s1_kernel) wherever it applies, Kdim 64 / 128 / 256;
-// 1 = Kdim 64 / 128 only (round 5; the 256-deep form runs one workgroup per CU with 128 weight VGPRs per wave:
-// ResNet-50 22.62 -> 22.31 ms/step interleaved A/B, profiles/r6_iteration_log.txt); 0 = off (A/B)
-int g_conv_s1 = -1;
-static bool s1_applies(const ConvArgs* a) {
-  if (g_conv_s1 < 0) {
-    const char* e = getenv("BIGDL_CONV_S1");
-    g_conv_s1 = e ? atoi(e) : 2;
-  }
-  if (!g_conv_s1 || a->out32 || !a->ident_out || a->ntaps != 1 || a->tap_h[0] || a->tap_w[0] || a->tap_k[0]) return false;
-  if (a->mul_h != 1 || a->mul_w != 1 || a->Hs != a->OH || a->Ws != a->OW) return false;
-  // BIGDL_CONV_S1 = 2 also takes Kdim 256 (128 VGPRs of weights per wave, 16-pixel wave tiles); 3 = Kdim 256 only
-  // without the extended epilogue (addend / consumer-BN reduction: data gradients stay on the tile kernels)
-  const bool ext = a->addend != nullptr || (a->bnred != nullptr && a->stats == nullptr);
-  if ((a->Kdim != 64 && a->Kdim != 128 && !(a->Kdim == 256 && (g_conv_s1 == 2 || (g_conv_s1 == 3 && !ext)))) ||
-      a->Cs != a->Kdim || (a->Ncol % 64) || (a->ldo % 8) || (a->ldw % 8))
-    return false;
-  // the epilogue operands go through 32-bit buffer offsets (bytes of an [M][ldo] bf16 tensor, below the OOB offset)
-  if (((size_t)(a->M - 1) * a->ldo + a->Ncol) * 2 >= 0x7ff00000u) return false;
-  // the consumer-BN ReLU mask as a bf16 z tensor (BIGDL_BN_ZMASK=0) is left to the tile kernels
-  if (a->bnred && !a->stats && a->bnz && !a->bnzm) return false;
-  // a BN applied on load (ConvArgs::pre) only with the forward epilogues (bias, statistics, ReLU; no addend)
-  if (a->pre && (a->addend || (a->bnred && !a->stats))) return false;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  return al(a->src) && al(a->wt) && al(a->out) && al(a->addend) && al(a->bnx) && al(a->bnz);
 }
 
 template <int K, int CG, int BMW, bool F32T, bool EXT, bool PRE = false>
 void launch_s1(const ConvArgs& a, hipStream_t st) {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
   const int nchb = a.Ncol / (64 * CG);
   const int tiles = (a.M + BMW * (4 / CG) - 1) / (BMW * (4 / CG));
   constexpr int occ = K >= 256 ? 1 : 2;            // workgroups per CU (K = 256: 128 weight VGPRs per wave)
-  int per = std::max(1, (occ * cus) / nchb);
+  int per = std::max(1, (occ * conv_cus()) / nchb);
   per = std::min(per, tiles);
   conv_nt_s1_kernel<K, CG, BMW, F32T, EXT, PRE><<<dim3(per * nchb), dim3(256), 0, st>>>(a);
 }
@@ -2999,7 +2914,7 @@ void launch_s1_cg(const ConvArgs& a, hipStream_t st) {
   }
 }
 
-static void launch_s1_any(const ConvArgs& a, hipStream_t st) {
+void launch_s1_any(const ConvArgs& a, hipStream_t st) {
   const int cg = (a.Ncol % 256 == 0) ? 4 : (a.Ncol % 128 == 0) ? 2 : 1;
   if (a.Kdim == 64) {
     if (cg == 4) launch_s1_cg<64, 4>(a, st);
@@ -3016,279 +2931,185 @@ static void launch_s1_any(const ConvArgs& a, hipStream_t st) {
   }
 }
 
-int g_conv_impl = -1;
-int conv_impl() {
-  if (g_conv_impl < 0) {
-    const char* e = getenv("BIGDL_CONV_IMPL");
-    g_conv_impl = e ? atoi(e) : 1;
-  }
-  return g_conv_impl;
+// 256 x 256 8-wave kernel: fast-K over 32-channel steps, aligned bf16 output, at least 256 output channels, at least
+// 4 K-steps of 32. Returns 0 (not picked) or the K split (1 = none): grids below one workgroup per CU are split along
+// K (>= 8 K-steps per split) so every CU gets work.
+int w8_pick(const ConvArgs* a) {
+  const int on = sw().w8;
+  if (!on || a->out32 || (a->Cs % 32) || (a->Ncol & 7) || (a->ldo & 7) || a->Ncol < 256 || a->Kdim < 128) return 0;
+  const long tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
+  const int nk = a->Kdim / 32;
+  if (tiles >= 200 || on == 2) return 1;
+  int split = (int)((320 + tiles - 1) / tiles);
+  split = std::min(split, std::max(1, nk / 8));
+  split = std::min(split, 8);
+  return std::max(split, 1);
 }
 
-}  // namespace
-
-extern "C" {
-
-void bigdl_set_conv_impl(int impl) { g_conv_impl = impl; }
-void bigdl_set_conv_s1(int v) { g_conv_s1 = v; }
-void bigdl_set_conv_sk(int v) { g_conv_sk = v; }
-void bigdl_set_conv_g4(int v) { g_conv_g4 = v; }
-void bigdl_set_conv_shortk(int v) { g_conv_shortk = v; }
-int g_wgrad_p8 = -1;
-void bigdl_set_conv_p8(int v) { g_conv_p8 = v; }
-void bigdl_set_wgrad_p8(int v) { g_wgrad_p8 = v; }
-int bigdl_get_conv_g4() { return g4_pick(); }
-int bigdl_get_conv_impl() { return conv_impl(); }
-
-// Forward or data-gradient implicit GEMM. Returns 0 on success, negative on unsupported shapes.
-long bigdl_conv_nt_plan(ConvArgs* a) {
-  a->ksplit = 0;
-  if (a->Cs % 8 != 0 || a->M <= 0 || conv_impl() < 1) return 0;
-  if (a->pstride > 0 && a->pstride != a->Cs) return 0;   // overlapping windows: g4 only, no split-K
-  if (conv_impl() == 1 && s1_applies(a)) return 0;
-  if (conv_impl() == 1 && bigdl_conv_halo_applies(a)) return 0;
-  if (conv_impl() == 1 && bigdl_stem_fwd_applies(a)) return 0;
-  if (g_conv_p8 < 0) (void)p8_pick(a);      // reads BIGDL_CONV_P8 once
-  const int sk = sk_pick(a);
-  if (sk > 0) {
-    a->ksplit = -sk;                        // stream-K: slots per tile (negative marks the mode)
-    const long tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-    return tiles * sk * 65536L + tiles;     // fp32 slots + one ticket word per tile
-  }
-  const int p8 = conv_impl() == 1 ? p8_pick(a) : 0;
-  if (p8 > 1) {
-    a->ksplit = p8;
-    return (long)p8 * a->M * a->Ncol;
-  }
-  if (p8 == 1) return 0;
-  const int k = w8_pick(a);
-  if (k > 1) {
-    a->ksplit = k;
-    return (long)k * a->M * a->Ncol;
-  }
-  return 0;
+// The 256 x 256 phase-interleaved kernel (ConvSwitches::p8). Returns 0 (not used), 1 (one pass) or the K split.
+int p8_pick(const ConvArgs* a) {
+  const int on = sw().p8;
+  // K tail (one tap, Cs % 64 != 0, e.g. a 10000-word vocabulary projection's data gradient): granules past Kdim zero
+  const bool ktail = (a->Cs % 64) != 0 && a->ntaps == 1 && a->Cs % 8 == 0 && a->Kdim == a->Cs;
+  if (!on || a->out32 || ((a->Cs % 64) && !ktail) || (a->Ncol & 7) || (a->ldo & 7) || a->Kdim < 128) return 0;
+  // auto: deep reductions only. Per layer (tools/conv_roofline.py, ResNet-50 b256) the one-workgroup-per-CU tile wins
+  // from K = 1024 up (3x3 over 256 channels 101 -> 86 us) and loses below, where its prologue / epilogue are not
+  // hidden by a co-resident workgroup (1x1 512 -> 1024 stride 2: 103 -> 147 us)
+  if (on == 1 && (a->Ncol < 256 || a->Kdim < 1024)) return 0;
+  const long tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
+  const int nk = a->Kdim / 64;
+  if (tiles >= 160) return 1;
+  // split-K measured slower than the 256 x 128 deep-K kernel on the small ResNet grids (12544 x 512, K 4608:
+  // 452 vs 544 TF/s, tools/gemm_ceiling.py): auto mode leaves grids under 160 tiles to the other kernels
+  if (on == 1) return 0;
+  int split = (int)((256 + tiles - 1) / tiles);
+  split = std::min(split, std::max(1, nk / 4));
+  split = std::min(split, 8);
+  return std::max(split, 1);
 }
 
-int bigdl_conv_pre_applies(const ConvArgs* a) {
-  if (a->Cs % 8 != 0 || a->Kdim != a->ntaps * a->Cs || a->M <= 0 || a->pstride > 0 || conv_impl() != 1) return 0;
-  if (bigdl_stem_fwd_applies(a)) return 0;
-  return (s1_applies(a) || bigdl_conv_halo_applies(a)) ? 1 : 0;
+// Stream-K for the P8 kernel (ConvSwitches::sk). Returns the (tile, segment) slots per tile, 0 when not used.
+int sk_pick(const ConvArgs* a) {
+  const ConvSwitches& s = sw();
+  if (!s.sk || s.impl != 1 || a->out32 || (a->Cs % 64) || (a->Ncol & 7) || (a->ldo & 7)) return 0;
+  if (s.p8 == 0) return 0;
+  if (s.sk == 1 && (a->Ncol < 256 || a->Kdim < s.sk_k)) return 0;
+  const long tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
+  const int G = conv_cus();
+  const int nk = a->Kdim / 64;
+  const double eff = (double)tiles / (double)(((tiles + G - 1) / G) * G);
+  if (s.sk == 1 && eff >= 0.85) return 0;
+  const long q = (tiles * nk) / G;
+  if (q < 4) return 0;                      // ranges too short for the pipeline
+  return (int)(nk / q + 2);
 }
 
-void bigdl_conv_addend_stride(ConvArgs* a, int sh, int sw, int add_h, int add_w) {
-  // reciprocal for q = __umulhi(x, r) == x / d, exact while x * d < 2^32 (d >= 2)
-  auto rcp = [](int d) { return d >= 2 ? (unsigned)((1ull << 32) / (unsigned)d) + 1u : 0u; };
-  const bool on = sh > 1 || sw > 1;
-  a->add_sh = on ? sh : 1; a->add_sw = on ? sw : 1;
-  a->add_H = on ? add_h : 0; a->add_W = on ? add_w : 0;
-  a->add_mow = rcp(a->OW); a->add_moh = rcp(a->OH); a->add_msh = rcp(sh); a->add_msw = rcp(sw);
+// The streaming 1x1 kernel (ConvSwitches::s1) takes this GEMM
+bool s1_applies(const ConvArgs* a) {
+  const int on = sw().s1;
+  if (!on || a->out32 || !a->ident_out || a->ntaps != 1 || a->tap_h[0] || a->tap_w[0] || a->tap_k[0]) return false;
+  if (a->mul_h != 1 || a->mul_w != 1 || a->Hs != a->OH || a->Ws != a->OW) return false;
+  const bool ext = a->addend != nullptr || (a->bnred != nullptr && a->stats == nullptr);
+  if ((a->Kdim != 64 && a->Kdim != 128 && !(a->Kdim == 256 && (on == 2 || (on == 3 && !ext)))) ||
+      a->Cs != a->Kdim || (a->Ncol % 64) || (a->ldo % 8) || (a->ldw % 8))
+    return false;
+  // the epilogue operands go through 32-bit buffer offsets (bytes of an [M][ldo] bf16 tensor, below the OOB offset)
+  if (((size_t)(a->M - 1) * a->ldo + a->Ncol) * 2 >= 0x7ff00000u) return false;
+  // the consumer-BN ReLU mask as a bf16 z tensor (BIGDL_BN_ZMASK=0) is left to the tile kernels
+  if (a->bnred && !a->stats && a->bnz && !a->bnzm) return false;
+  // a BN applied on load (ConvArgs::pre) only with the forward epilogues (bias, statistics, ReLU; no addend)
+  if (a->pre && (a->addend || (a->bnred && !a->stats))) return false;
+  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  return al(a->src) && al(a->wt) && al(a->out) && al(a->addend) && al(a->bnx) && al(a->bnz);
 }
 
-// The subsampled addend lives in the streaming 1x1 EXT epilogue and in nt_epilogue_lds as the multi-stage tile kernel
-// calls it (identity rows): 1 when bigdl_conv_nt's dispatch below ends in one of the two for `a`.
-int bigdl_conv_addend_stride_applies(const ConvArgs* a) {
-  if (!a->addend || a->add_sh < 2 || a->add_sw < 2 || a->addzm || a->out32 || a->pre || a->stats) return 0;
-  if (conv_impl() != 1 || a->Cs % 8 != 0 || a->Kdim != a->ntaps * a->Cs || a->M <= 0 || a->pstride > 0) return 0;
-  if (!a->ident_out || (a->Ncol & 7) || a->ldo != a->Ncol || a->OH < 2 || a->OW < 2) return 0;
-  if (a->add_H != (a->OH + a->add_sh - 1) / a->add_sh || a->add_W != (a->OW + a->add_sw - 1) / a->add_sw) return 0;
+ConvChoice conv_choice(int kernel, int BM = 0, int BN = 0, int stages = 0) {
+  ConvChoice c{};
+  c.kernel = kernel; c.BM = BM; c.BN = BN; c.stages = stages; c.ksplit = 1;
+  return c;
+}
+
+// Operand preconditions of a subsampled addend (ConvArgs::add_sh), whichever kernel implements it
+bool addend_stride_operands_ok(const ConvArgs* a) {
+  if (!a->addend || a->add_sh < 2 || a->add_sw < 2 || a->addzm || a->out32 || a->pre || a->stats) return false;
+  if (a->pstride > 0 || !a->ident_out || (a->Ncol & 7) || a->ldo != a->Ncol || a->OH < 2 || a->OW < 2) return false;
+  if (a->add_H != (a->OH + a->add_sh - 1) / a->add_sh || a->add_W != (a->OW + a->add_sw - 1) / a->add_sw) return false;
   // exact multiply-high divisions of row numbers, 32-bit byte offsets below the out-of-range offset
   const unsigned long long dmax = std::max(std::max(a->OH, a->OW), std::max(a->add_sh, a->add_sw));
-  if ((unsigned long long)a->M * dmax >= (1ull << 32)) return 0;
-  if (((size_t)(a->M - 1) * a->ldo + a->Ncol) * 2 >= 0x7ff00000u) return 0;
-  if ((reinterpret_cast<uintptr_t>(a->addend) & 15) != 0) return 0;
-  if (bigdl_stem_fwd_applies(a)) return 0;
-  if (s1_applies(a)) return 1;
-  if (bigdl_conv_halo_applies(a)) return 0;
-  if (sk_pick(a) > 0 || p8_pick(a) != 0 || w8_pick(a) != 0) return 0;
-  const bool fastk = (a->Cs % BK) == 0;
-  static const bool p3auto = [] { const char* e = getenv("BIGDL_CONV_P3AUTO"); return e ? atoi(e) != 0 : true; }();
-  const bool p3_pick = p3auto && a->M <= 50176 && a->Kdim >= 1024;
-  const long p3_tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 127) / 128);
-  return (g4_pick() && (a->Cs % 32 == 0 || (g4_slowk() && a->Kdim % 8 == 0)) &&
-          (g4_pick() == 5 || !(p3_pick && fastk && p3_tiles >= 256))) ? 1 : 0;
+  if ((unsigned long long)a->M * dmax >= (1ull << 32)) return false;
+  if (((size_t)(a->M - 1) * a->ldo + a->Ncol) * 2 >= 0x7ff00000u) return false;
+  return (reinterpret_cast<uintptr_t>(a->addend) & 15) == 0;
 }
 
-int bigdl_conv_nt(const ConvArgs* a, hipStream_t st) {
-  if (a->Cs % 8 != 0 || a->Kdim != a->ntaps * a->Cs || a->ntaps < 1 || a->ntaps > CONV_MAX_TAPS) return -1;
-  // a subsampled addend only on the kernels that implement it (the caller materialises it otherwise)
-  if (a->addend && (a->add_sh > 1 || a->add_sw > 1) && !bigdl_conv_addend_stride_applies(a)) return -6;
-  if (a->pre) {     // a BN applied on load: only the kernels that implement it (the caller materialises otherwise)
-    if (!bigdl_conv_pre_applies(a)) return -5;
-    if (s1_applies(a)) launch_s1_any(*a, st);
-    else if (bigdl_conv_halo(a, st) != 0) return -5;
-    HIP_LAUNCH_CHECK();
-    return 0;
+// The ladder: first kernel that takes the GEMM, in order of preference.
+ConvChoice conv_nt_ladder(const ConvArgs* a) {
+  const ConvSwitches& s = sw();
+  if (a->Cs % 8 != 0 || a->Kdim != a->ntaps * a->Cs || a->ntaps < 1 || a->ntaps > CONV_MAX_TAPS)
+    return conv_choice(CONV_ERR_SHAPE);
+  if (!a->pre) {     // (a `pre` call is held to the s1 / halo kernels, which take neither of these)
+    // the BN-backward reduction lives in the LDS-transposed epilogue only
+    if (a->bnred && (a->stats || a->bnx == nullptr || a->bnmean == nullptr || (a->Ncol & 7) || (a->ldo & 7)))
+      return conv_choice(CONV_ERR_BNRED);
+    // fp32 output exists in the LDS-transposed epilogue only (aligned columns), without stats / BN / ReLU / addend
+    if (a->out32 && ((a->Ncol & 7) || (a->ldo & 7) || a->stats || a->bnred || a->relu || a->addend))
+      return conv_choice(CONV_ERR_OUT32);
   }
-  // the BN-backward reduction lives in the LDS-transposed epilogue only
-  if (a->bnred && (a->stats || a->bnx == nullptr || a->bnmean == nullptr || (a->Ncol & 7) || (a->ldo & 7))) return -2;
-  // fp32 output exists in the LDS-transposed epilogue only (aligned columns), without stats / BN / ReLU / addend
-  if (a->out32 && ((a->Ncol & 7) || (a->ldo & 7) || a->stats || a->bnred || a->relu || a->addend)) return -3;
-  if (a->M <= 0) return 0;
+  if (a->M <= 0) return conv_choice(CONV_NONE);
   const bool fastk = (a->Cs % BK) == 0;
-  const int impl = conv_impl();
-  if (impl == 1 && bigdl_stem_fwd_applies(a) && bigdl_stem_fwd(a, st) == 0) {
-    HIP_LAUNCH_CHECK();
-    return 0;
-  }
+  const int impl = s.impl;
+  const int bn = a->Ncol <= 64 ? 64 : 128;
+  if (impl == 1 && bigdl_stem_fwd_applies(a)) return conv_choice(CONV_STEM);
   if (a->pstride > 0 && a->pstride != a->Cs) {   // overlapping-window source: the g4 kernel is the one that reads it
-    if ((a->Ncol & 7) || (a->ldo & 7) || a->out32 || a->ws || a->bnred || !(fastk || a->Kdim % 8 == 0)) return -4;
-    if (a->Ncol <= 64) launch_nt_g4<64, 3>(*a, st);
-    else launch_nt_g4<128, 3>(*a, st);
-    HIP_LAUNCH_CHECK();
-    return 0;
+    if ((a->Ncol & 7) || (a->ldo & 7) || a->out32 || a->bnred || !(fastk || a->Kdim % 8 == 0))
+      return conv_choice(CONV_ERR_WINDOW);
+    return conv_choice(CONV_G4, 128, bn, 3);
   }
-  if (impl == 1 && s1_applies(a)) {
-    launch_s1_any(*a, st);
-    HIP_LAUNCH_CHECK();
-    return 0;
+  if (impl == 1 && s1_applies(a)) return conv_choice(CONV_S1);
+  if (impl == 1 && bigdl_conv_halo_applies(a)) return conv_choice(CONV_HALO);
+  const long tiles256 = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
+  const int sk = sk_pick(a);
+  if (sk > 0) {
+    ConvChoice c = conv_choice(CONV_P8_SK, 256, 256);
+    c.sk_slots = sk;
+    c.ws_floats = tiles256 * sk * 65536L + tiles256;     // fp32 slots + one ticket word per tile
+    return c;
   }
-  if (impl == 1 && bigdl_conv_halo_applies(a) && bigdl_conv_halo(a, st) == 0) {
-    HIP_LAUNCH_CHECK();
-    return 0;
+  const int p8 = impl == 1 ? p8_pick(a) : 0;
+  if (p8 > 0) {
+    ConvChoice c = conv_choice(p8 > 1 ? CONV_P8_SPLIT : CONV_P8, 256, 256);
+    c.ktail = (a->Cs % 64) != 0;
+    c.ksplit = p8;
+    c.ws_floats = p8 > 1 ? (long)p8 * a->M * a->Ncol : 0;
+    return c;
   }
-  if (a->ksplit < 0 && a->ws != nullptr) {  // stream-K P8 (bigdl_conv_nt_plan)
-    ConvArgs b = *a;
-    b.ksplit = -a->ksplit;
-    const long tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-    bigdl_fill_bytes(b.ws + tiles * b.ksplit * 65536L, 0, tiles * 4, st);   // tickets (a kernel: graph-safe)
-    const dim3 grid((unsigned)std::min<long>(sk_cus(), tiles * (a->Kdim / 64)));
-    conv_nt_p8_kernel<false, 0, true><<<grid, dim3(512), 0, st>>>(b);
-    HIP_LAUNCH_CHECK();
-    return 0;
+  const int w8 = impl == 1 ? w8_pick(a) : 0;
+  if (w8 > 0) {
+    ConvChoice c = conv_choice(w8 > 1 ? CONV_W8_SPLIT : CONV_W8, 256, 256);
+    c.ksplit = w8;
+    c.ws_floats = w8 > 1 ? (long)w8 * a->M * a->Ncol : 0;
+    return c;
   }
   const long p3_tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 127) / 128);
-  const long tiles128 = (long)((a->M + 127) / 128) * ((a->Ncol + (a->Ncol <= 64 ? 63 : 127)) / (a->Ncol <= 64 ? 64 : 128));
+  const long tiles128 = (long)((a->M + 127) / 128) * ((a->Ncol + bn - 1) / bn);
   const bool aligned_out = (a->Ncol & 7) == 0 && (a->ldo & 7) == 0;   // the persistent kernel has no fallback epilogue
-  // deep-K layers on small pixel grids (ResNet stages 4-5: <= 50k output pixels, K >= 1024) run faster on the
-  // 8-wave deep-pipelined kernel (tools/bench_conv.py, impl 1 vs 2); BIGDL_CONV_P3AUTO=0 keeps them on impl 1
-  static const bool p3auto = [] { const char* e = getenv("BIGDL_CONV_P3AUTO"); return e ? atoi(e) != 0 : true; }();
-  const bool p3_pick = impl == 2 || (impl == 1 && p3auto && a->M <= 50176 && a->Kdim >= 1024);
-  const int p8 = impl == 1 ? p8_pick(a) : 0;
-  const int w8 = (impl == 1 && p8 == 0) ? w8_pick(a) : 0;
-  // K tail (one tap, Cs % 64 != 0, e.g. a 10000-word vocabulary projection's data gradient): granules past Kdim zero
-  const bool p8_ktail = (a->Cs % 64) != 0;
-  if (p8 > 1 && a->ksplit == p8 && a->ws != nullptr) {
-    const int nwg = ((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-    if (p8_ktail) conv_nt_p8_kernel<true, 64><<<dim3(nwg, p8), dim3(512), 0, st>>>(*a);
-    else conv_nt_p8_kernel<true><<<dim3(nwg, p8), dim3(512), 0, st>>>(*a);
-    long rpb = 0;
-    const dim3 grid = splitk_grid(a->M, a->Ncol, &rpb);
-    conv_splitk_epilogue_kernel<<<grid, dim3(256), 0, st>>>(*a, rpb);
-  } else if (p8 == 1) {
-    const int nwg = ((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-    static const int abl = [] { const char* e = getenv("BIGDL_P8_ABL"); return e ? atoi(e) : 0; }();
-    switch (p8_ktail ? 64 : abl) {
-      case 64: conv_nt_p8_kernel<false, 64><<<dim3(nwg), dim3(512), 0, st>>>(*a); break;
-      case 1: conv_nt_p8_kernel<false, 1><<<dim3(nwg), dim3(512), 0, st>>>(*a); break;
-      case 2: conv_nt_p8_kernel<false, 2><<<dim3(nwg), dim3(512), 0, st>>>(*a); break;
-      case 4: conv_nt_p8_kernel<false, 4><<<dim3(nwg), dim3(512), 0, st>>>(*a); break;
-      case 8: conv_nt_p8_kernel<false, 8><<<dim3(nwg), dim3(512), 0, st>>>(*a); break;
-      case 16: conv_nt_p8_kernel<false, 16><<<dim3(nwg), dim3(512), 0, st>>>(*a); break;
-      case 32: conv_nt_p8_kernel<false, 32><<<dim3(nwg), dim3(512), 0, st>>>(*a); break;
-      case 10: conv_nt_p8_kernel<false, 10><<<dim3(nwg), dim3(512), 0, st>>>(*a); break;
-      default: conv_nt_p8_kernel<false><<<dim3(nwg), dim3(512), 0, st>>>(*a);
-    }
-  } else if (w8 > 1 && a->ksplit == w8 && a->ws != nullptr) {
-    const int nwg = ((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-    conv_nt_w8_kernel<true><<<dim3(nwg, w8), dim3(512), 0, st>>>(*a);
-    long rpb = 0;
-    const dim3 grid = splitk_grid(a->M, a->Ncol, &rpb);
-    conv_splitk_epilogue_kernel<<<grid, dim3(256), 0, st>>>(*a, rpb);
-  } else if (w8 == 1) {
-    const int nwg = ((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-    conv_nt_w8_kernel<false><<<dim3(nwg), dim3(512), 0, st>>>(*a);
-  } else if (impl == 1 && g4_pick() && aligned_out && (a->Cs % 32 == 0 || (g4_slowk() && a->Kdim % 8 == 0)) &&
-             (g4_pick() == 5 || !(p3_pick && fastk && p3_tiles >= 256))) {
-    const long tiles256 = (long)((a->M + 255) / 256) * ((a->Ncol + 127) / 128);
-    if (a->Ncol > 64 && (g4_pick() == 7 || (g4_pick() == 6 && tiles256 >= 512))) {
-      launch_nt_g4<128, 3, 256>(*a, st);
-    } else if (conv_shortk() && fastk && a->Kdim <= 64 && a->Ncol <= 64) {
-      launch_nt_g4<64, 2>(*a, st);   // (the 128-wide tile needs 168 VGPRs: no fourth workgroup)
-    } else if (g4_pick() != 4) {
-      if (a->Ncol <= 64) launch_nt_g4<64, 3>(*a, st);
-      else launch_nt_g4<128, 3>(*a, st);
-    } else {
-      if (a->Ncol <= 64) launch_nt_g4<64, 4>(*a, st);
-      else launch_nt_g4<128, 4>(*a, st);
-    }
-  } else if (fastk && p3_pick && p3_tiles >= 256) {
-    if (a->Ncol <= 64) launch_nt_p3<64, 8, 1>(*a, st);
-    else launch_nt_p3<128, 4, 2>(*a, st);
-  } else if (fastk && impl == 3 && aligned_out && tiles128 > 2 * 256) {
-    if (a->Ncol <= 64) launch_nt_pers<128, 64, 2>(*a, st);
-    else launch_nt_pers<128, 128, 2>(*a, st);
-  } else if (fastk && impl >= 1 && a->Kdim == BK && aligned_out && conv_onestage()) {
-    if (a->Ncol <= 64) launch_nt_glds<128, 64, 2, true, 1>(*a, st);
-    else launch_nt_glds<128, 128, 2, true, 1>(*a, st);
-  } else if (fastk && impl >= 1) {
-    if (a->Ncol <= 64) launch_nt_glds<128, 64, 2>(*a, st);
-    else launch_nt_glds<128, 128, 2>(*a, st);
-  } else if (!fastk && impl >= 1 && glds_slowk()) {
-    if (a->Ncol <= 64) launch_nt_glds<128, 64, 2, false>(*a, st);
-    else launch_nt_glds<128, 128, 2, false>(*a, st);
-  } else if (a->Ncol <= 64) {
-    launch_nt<128, 64, 2>(*a, fastk, st);
-  } else {
-    launch_nt<128, 128, 2>(*a, fastk, st);
+  const bool p3_pick = impl == 2 || (impl == 1 && s.p3auto && a->M <= 50176 && a->Kdim >= 1024);
+  if (impl == 1 && s.g4 && aligned_out && (a->Cs % 32 == 0 || (s.g4_slowk && a->Kdim % 8 == 0)) &&
+      (s.g4 == 5 || !(p3_pick && fastk && p3_tiles >= 256))) {
+    if (a->Ncol > 64 && (s.g4 == 7 || (s.g4 == 6 && p3_tiles >= 512))) return conv_choice(CONV_G4, 256, 128, 3);
+    // (the 128-wide tile needs 168 VGPRs: no fourth workgroup)
+    if (s.shortk && fastk && a->Kdim <= 64 && a->Ncol <= 64) return conv_choice(CONV_G4, 128, 64, 2);
+    return conv_choice(CONV_G4, 128, bn, s.g4 != 4 ? 3 : 4);
   }
-  HIP_LAUNCH_CHECK();
-  return 0;
+  if (fastk && p3_pick && p3_tiles >= 256) return conv_choice(CONV_P3, 256, bn);
+  if (fastk && impl == 3 && aligned_out && tiles128 > 2 * 256) return conv_choice(CONV_PERS, 128, bn, 2);
+  if (fastk && impl >= 1 && a->Kdim == BK && aligned_out && s.onestage) return conv_choice(CONV_GLDS_ONESTAGE, 128, bn, 1);
+  if (fastk && impl >= 1) return conv_choice(CONV_GLDS, 128, bn, 2);
+  if (!fastk && impl >= 1 && s.glds_slowk) return conv_choice(CONV_GLDS_SLOWK, 128, bn, 2);
+  return conv_choice(CONV_REG, 128, bn, 1);
 }
 
 // 64-wide output-channel layers with a deep reduction (stem 7x7, 3x3 over 64 channels) run half-empty 128x128
 // tiles; the register-staged atomic kernel is faster there (measured per layer, profiles/r1_ab_wgrad.txt)
-static bool wgrad_prefers_atomic(const WgradArgs* a) {
-  // BIGDL_WGRAD_ATOMIC: 1 (default) this rule, 0 never, 2 always (per-layer A/B runs); never in deterministic mode
-  static const int on = [] { const char* e = getenv("BIGDL_WGRAD_ATOMIC"); return e ? atoi(e) : 1; }();
+bool wgrad_prefers_atomic(const WgradArgs* a) {
+  const int on = sw().wgrad_atomic;
   if (bigdl_deterministic()) return false;
   return on == 2 || (on == 1 && a->Ncol <= 64 && a->Kdim > 256);
 }
 
-int g_wgrad_g3 = -1;
-// BIGDL_WGRAD_G3=1: the 3-stage counted-vmcnt weight-gradient kernel in place of the 2-stage one
-static bool wgrad_g3() {
-  if (g_wgrad_g3 < 0) {
-    const char* e = getenv("BIGDL_WGRAD_G3");
-    g_wgrad_g3 = e ? atoi(e) : 0;
-  }
-  return g_wgrad_g3 != 0;
-}
-void bigdl_set_wgrad_g3(int v) { g_wgrad_g3 = v; }
-int bigdl_get_wgrad_g3() { return wgrad_g3() ? 1 : 0; }
-
-int g_wgrad_tr_asm = -1;
-// BIGDL_WGRAD_TR_ASM: 1 (default) = the weight-gradient kernels read their fragments with inline-assembly
-// transposing reads and hand-placed waits (lds_tr.h); 0 = through the compiler intrinsic, which drains the LDS-DMA
-// in front of every group of reads. Same kernels (a template flag), same results bit for bit; for A/B runs.
-static bool wgrad_tr_asm() {
-  if (g_wgrad_tr_asm < 0) {
-    const char* e = getenv("BIGDL_WGRAD_TR_ASM");
-    g_wgrad_tr_asm = e ? atoi(e) : 1;
-  }
-  return g_wgrad_tr_asm != 0;
-}
-void bigdl_set_wgrad_tr_asm(int v) { g_wgrad_tr_asm = v; }
-int bigdl_get_wgrad_tr_asm() { return wgrad_tr_asm() ? 1 : 0; }
-
-static void launch_wgrad_g3(const WgradArgs& a, int blocks, hipStream_t st) {
-  if (wgrad_tr_asm()) conv_wgrad_g3_kernel<true><<<dim3(blocks), dim3(256), 0, st>>>(a);
+void launch_wgrad_g3(const WgradArgs& a, int blocks, hipStream_t st) {
+  if (sw().wgrad_tr_asm) conv_wgrad_g3_kernel<true><<<dim3(blocks), dim3(256), 0, st>>>(a);
   else conv_wgrad_g3_kernel<false><<<dim3(blocks), dim3(256), 0, st>>>(a);
 }
-static void launch_wgrad_glds(const WgradArgs& a, int blocks, hipStream_t st) {
-  if (wgrad_tr_asm()) conv_wgrad_glds_kernel<true><<<dim3(blocks), dim3(256), 0, st>>>(a);
+void launch_wgrad_glds(const WgradArgs& a, int blocks, hipStream_t st) {
+  if (sw().wgrad_tr_asm) conv_wgrad_glds_kernel<true><<<dim3(blocks), dim3(256), 0, st>>>(a);
   else conv_wgrad_glds_kernel<false><<<dim3(blocks), dim3(256), 0, st>>>(a);
 }
 
-// BIGDL_WGRAD_P8: 1 (default) = conv_wgrad_p8_kernel where it measured faster (below), 2 = on every layer with
-// Ncol >= 256 and Kdim >= 256 (tests / A/B), 0 = off.
-// Returns its pixel split (>= 1) or 0 when it does not apply; sets m_per_split.
-static int p8w_pick(WgradArgs* a) {
-  if (g_wgrad_p8 < 0) {
-    const char* e = getenv("BIGDL_WGRAD_P8");
-    g_wgrad_p8 = e ? atoi(e) : 1;
-  }
-  if (!g_wgrad_p8 || conv_impl() < 1 || a->Ncol < 256 || a->Kdim < 256 || (a->Cs % 8) ||
-      (a->Ncol % 8) || (a->Kdim % 8) || a->M <= 0)
+// conv_wgrad_p8_kernel (ConvSwitches::wgrad_p8): its pixel split (>= 1) or 0 when it does not apply; sets *mps_out.
+int p8w_pick(const WgradArgs* a, int* mps_out) {
+  const ConvSwitches& s = sw();
+  if (!s.wgrad_p8 || s.impl < 1 || a->Ncol < 256 || a->Kdim < 256 || (a->Cs % 8) || (a->Ncol % 8) || (a->Kdim % 8) ||
+      a->M <= 0)
     return 0;
   const long tiles = (long)((a->Ncol + 255) / 256) * ((a->Kdim + 255) / 256);
   // Default: GEMM-shaped (1 x 1) weight gradients with >= 32 output tiles — Linear / LSTM projections, where it reads
@@ -3297,7 +3118,7 @@ static int p8w_pick(WgradArgs* a) {
   // inside the training step its 128 KB-LDS workgroups on the weight-gradient side stream cost the concurrent data-
   // gradient chain more than they save (26.05 vs 25.72 ms/step, profiles/r4_wgrad_p8_ab.txt); on 1x1 layers with few
   // tiles its deep pixel split turns into fp32 partial traffic
-  if (g_wgrad_p8 == 1 && !(a->R * a->S == 1 && tiles >= 32)) return 0;
+  if (s.wgrad_p8 == 1 && !(a->R * a->S == 1 && tiles >= 32)) return 0;
   const long steps = (a->M + 63) / 64;
   // pixel split: one workgroup per CU, so pick the split (<= 8, >= 8 pixel steps each, <= 256 MB of fp32 partials)
   // whose grid fills its last dispatch round best (vocab 160 tiles: 2 splits = 320 workgroups = 1.25 rounds ran at
@@ -3314,175 +3135,293 @@ static int p8w_pick(WgradArgs* a) {
   long mps = (a->M + splits - 1) / splits;
   mps = (mps + 63) / 64 * 64;
   splits = (a->M + mps - 1) / mps;
-  a->m_per_split = (int)mps;
+  *mps_out = (int)mps;
   return (int)splits;
 }
 
-int bigdl_conv_wgrad_uses_p8(const WgradArgs* a_in) {
-  WgradArgs a = *a_in;
-  return p8w_pick(&a) > 0 ? 1 : 0;
+// pixel split of the 128 x 128 kernels: at most `splits`, whole WBM-pixel LDS stages per split
+void wgrad_split(WgradChoice* c, int M, int splits) {
+  int mps = (M + splits - 1) / splits;
+  mps = (mps + WBM - 1) / WBM * WBM;
+  c->m_per_split = mps;
+  c->splits = (M + mps - 1) / mps;
 }
 
-// 1 when a weight gradient that is left to the 128 x 128 kernels runs the register-staged conv_wgrad_kernel
-// (no LDS-DMA build, or the half-empty-tile rule) instead of conv_wgrad_glds_kernel
-int bigdl_conv_wgrad_uses_register_kernel(const WgradArgs* a) {
-  return (conv_impl() < 1 || wgrad_prefers_atomic(a)) ? 1 : 0;
-}
-
-long bigdl_conv_wgrad_plan(WgradArgs* a) {
-  if (conv_impl() >= 1) {
-    const long sw = bigdl_stem_wgrad_plan(a);
-    if (sw > 0) {
-      a->splits = -1;                        // the pair-view stem kernel (stem_fwd.hip)
-      return sw;
+WgradChoice conv_wgrad_ladder(const WgradArgs* a) {
+  const ConvSwitches& s = sw();
+  WgradChoice c{};
+  if (s.impl >= 1) {
+    const long ws = bigdl_stem_wgrad_plan(a);
+    if (ws > 0) {
+      c.kernel = WGRAD_STEM; c.splits = -1; c.ws_floats = ws;     // (the kernel splits by workgroup, not by a.splits)
+      return c;
     }
   }
-  const int hs = bigdl_wgrad_halo_plan(a);
+  if (a->Cs % 8 != 0 || a->Ncol % 8 != 0 || a->Kdim % 8 != 0) { c.kernel = WGRAD_ERR_SHAPE; return c; }
+  WgradArgs b = *a;
+  const int hs = bigdl_wgrad_halo_plan(&b);
   if (hs > 0) {
-    a->splits = hs;
-    return hs > 1 ? (long)hs * a->Ncol * a->Kdim + (a->dbias ? (long)hs * a->Ncol : 0) : 0;
+    c.kernel = WGRAD_HALO; c.splits = hs; c.m_per_split = b.m_per_split;
+    c.ws_floats = hs > 1 ? (long)hs * a->Ncol * a->Kdim + (a->dbias ? (long)hs * a->Ncol : 0) : 0;
+    return c;
   }
-  const int p8w = p8w_pick(a);
+  const int p8w = p8w_pick(a, &c.m_per_split);
   if (p8w > 0) {
-    a->splits = p8w;
-    return p8w > 1 ? (long)p8w * a->Ncol * a->Kdim : 0;
+    const bool direct = a->R == 1 && a->S == 1 && a->sh == 1 && a->sw == 1 && a->ph == 0 && a->pw == 0 &&
+                        a->Hs == a->OH && a->Ws == a->OW;
+    c.kernel = direct ? WGRAD_P8_DIRECT : WGRAD_P8; c.splits = p8w;
+    c.ws_floats = p8w > 1 ? (long)p8w * a->Ncol * a->Kdim : 0;
+    return c;
   }
   const int tiles = ((a->Ncol + WT - 1) / WT) * ((a->Kdim + WT - 1) / WT);
-  if (conv_impl() < 1 || wgrad_prefers_atomic(a)) { a->splits = 0; return 0; }
-  // workspace split-K: ~2 workgroups per CU (512; the kernel runs beside the dgrad chain on the side stream, so
-  // fewer splits = less partial traffic wins: 26.37 vs 26.62 ms/step, profiles/r3_wgrad_wgs_ab.txt), >= 4 LDS stages per split
-  // (BIGDL_WGRAD_WGS overrides the workgroup target for A/B runs: fewer splits = fewer partials to reduce)
-  static const int target = [] { const char* e = getenv("BIGDL_WGRAD_WGS"); return e ? atoi(e) : 512; }();
-  int splits = (target + tiles - 1) / tiles;
-  const int maxsplit = (a->M + 8 * WBM - 1) / (8 * WBM);
-  if (splits > maxsplit) splits = maxsplit;
-  if (splits < 1) splits = 1;
-  int mps = (a->M + splits - 1) / splits;
-  mps = (mps + WBM - 1) / WBM * WBM;
-  splits = (a->M + mps - 1) / mps;
-  a->m_per_split = mps;
-  a->splits = splits;
-  return splits > 1 ? (long)splits * a->Ncol * a->Kdim : 0;
-}
-
-static int conv_wgrad_impl(const WgradArgs* a_in, hipStream_t st);
-
-// Deterministic mode: the split kernels add their bias partials with one atomic per split, so the bias gradient is
-// taken out of them and summed by a one-row-block column sum (one atomic per channel); the weight gradient always
-// goes through the workspace partials + fixed-order reduce (no multi-split atomics, see bigdl_conv_wgrad_plan).
-int bigdl_conv_wgrad(const WgradArgs* a_in, hipStream_t st) {
-  if (bigdl_deterministic() && a_in->dbias != nullptr && (a_in->ldy % 8) == 0 && a_in->pre_x == nullptr) {
-    WgradArgs b = *a_in;
-    b.dbias = nullptr;
-    const int rc = conv_wgrad_impl(&b, st);
-    if (rc == 0) bigdl_colsum_bf16_ld(a_in->dy, a_in->dbias, a_in->M, a_in->Ncol, a_in->ldy, st, a_in->det_ws);
-    return rc;
-  }
-  return conv_wgrad_impl(a_in, st);
-}
-
-static int conv_wgrad_impl(const WgradArgs* a_in, hipStream_t st) {
-  WgradArgs a = *a_in;
-  if (a.pre_x) {    // dy formed on load from the consumer BN's backward: the pair-view stem kernel only
-    if (a.pre || a.splits != -1 || a.ws == nullptr || bigdl_stem_wgrad_plan(&a) <= 0) return -7;
-    const int rc = bigdl_stem_wgrad(&a, st);
-    HIP_LAUNCH_CHECK();
-    return rc;
-  }
-  if (a.pre) {      // a BN applied on load: the halo kernel only (the binding materialises everything else)
-    WgradArgs b = a;
-    const int hs = bigdl_wgrad_halo_plan(&b);
-    if (hs <= 0 || hs != a.splits || (hs > 1 && a.ws == nullptr)) return -6;
-    b.splits = hs;
-    b.ws = hs > 1 ? a.ws : nullptr;
-    const int rc = bigdl_wgrad_halo(&b, st);
-    HIP_LAUNCH_CHECK();
-    return rc;
-  }
-  if (a.splits == -1 && a.ws != nullptr && bigdl_stem_wgrad_plan(&a) > 0) {
-    const int rc = bigdl_stem_wgrad(&a, st);
-    HIP_LAUNCH_CHECK();
-    return rc;
-  }
-  if (a.Cs % 8 != 0 || a.Ncol % 8 != 0 || a.Kdim % 8 != 0) return -1;
-  {
-    WgradArgs b = a;
-    const int hs = bigdl_wgrad_halo_plan(&b);
-    if (hs > 0 && hs == a.splits && (hs == 1 || a.ws != nullptr)) {
-      b.splits = hs;
-      b.ws = hs > 1 ? a.ws : nullptr;
-      if (bigdl_wgrad_halo(&b, st) == 0) {
-        HIP_LAUNCH_CHECK();
-        return 0;
-      }
+  const bool dma = s.impl >= 1 && !wgrad_prefers_atomic(a);
+  if (dma) {
+    // workspace split-K: ~2 workgroups per CU (512; the kernel runs beside the dgrad chain on the side stream, so
+    // fewer splits = less partial traffic wins: 26.37 vs 26.62 ms/step, profiles/r3_wgrad_wgs_ab.txt), >= 4 LDS
+    // stages per split
+    int splits = (s.wgrad_wgs + tiles - 1) / tiles;
+    splits = std::max(1, std::min(splits, (a->M + 8 * WBM - 1) / (8 * WBM)));
+    wgrad_split(&c, a->M, splits);
+    if (c.splits > 1) {
+      c.kernel = s.wgrad_g3 ? WGRAD_G3_WS : WGRAD_GLDS_WS;
+      c.ws_floats = (long)c.splits * a->Ncol * a->Kdim;
+      return c;
     }
   }
-  {
-    WgradArgs b = a;
-    const int p8w = p8w_pick(&b);
-    if (p8w > 0 && p8w == a.splits && (p8w == 1 || a.ws != nullptr)) {
-      b.splits = p8w;
-      b.ws = a.ws;
-      const int tiles = ((a.Ncol + 255) / 256) * ((a.Kdim + 255) / 256);
-      const bool direct = a.R == 1 && a.S == 1 && a.sh == 1 && a.sw == 1 && a.ph == 0 && a.pw == 0 && a.Hs == a.OH &&
-                          a.Ws == a.OW;
-      const dim3 grid(tiles, p8w);
-      if (wgrad_tr_asm()) {
-        if (direct) conv_wgrad_p8_kernel<true, true><<<grid, dim3(512), 0, st>>>(b);
-        else conv_wgrad_p8_kernel<false, true><<<grid, dim3(512), 0, st>>>(b);
-      } else {
-        if (direct) conv_wgrad_p8_kernel<true, false><<<grid, dim3(512), 0, st>>>(b);
-        else conv_wgrad_p8_kernel<false, false><<<grid, dim3(512), 0, st>>>(b);
-      }
-      if (p8w > 1) {
-        const long n4 = (long)a.Ncol * a.Kdim / 4;
-        const int blocks = (int)std::min<long>((n4 + 255) / 256, 8192);
-        if ((reinterpret_cast<uintptr_t>(a.dw) & 15) == 0) wgrad_reduce_kernel<true><<<dim3(blocks, 1), 256, 0, st>>>(a.ws, a.dw, n4, p8w);
-        else wgrad_reduce_kernel<false><<<dim3(blocks, 1), 256, 0, st>>>(a.ws, a.dw, n4, p8w);
-      }
-      HIP_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  if (a.ws != nullptr && a.splits > 1 && conv_impl() >= 1) {
-    const int tiles = ((a.Ncol + WT - 1) / WT) * ((a.Kdim + WT - 1) / WT);
-    const int spad = (a.splits + 7) / 8 * 8;
-    if (wgrad_g3()) launch_wgrad_g3(a, tiles * spad, st);
-    else launch_wgrad_glds(a, tiles * spad, st);
-    const long n4 = (long)a.Ncol * a.Kdim / 4;
-    const int blocks = (int)std::min<long>((n4 + 255) / 256, 8192);
-    // ~2048 reduce workgroups in total, >= 4 splits per group, <= 64-way atomic contention
-    const int groups = (blocks >= 256 || bigdl_deterministic()) ? 1
-                                                               : std::max(1, std::min({2048 / blocks, a.splits / 4, 64}));
-    const dim3 rgrid(blocks, groups);
-    if ((reinterpret_cast<uintptr_t>(a.dw) & 15) == 0) wgrad_reduce_kernel<true><<<rgrid, 256, 0, st>>>(a.ws, a.dw, n4, a.splits);
-    else wgrad_reduce_kernel<false><<<rgrid, 256, 0, st>>>(a.ws, a.dw, n4, a.splits);
-    HIP_LAUNCH_CHECK();
-    return 0;
-  }
-  a.ws = nullptr;
-  const int tiles = ((a.Ncol + WT - 1) / WT) * ((a.Kdim + WT - 1) / WT);
-  // ~2 workgroups per CU in one dispatch wave; every split adds a full fp32 atomic pass over its
-  // tile, so also cap the atomic traffic (splits x |dW| x 4 B) at ~32 MB (~25 us at the chip rate).
+  // fp32 atomics into dW: ~2 workgroups per CU in one dispatch wave; every split adds a full fp32 atomic pass over its
+  // tile, so also cap the atomic traffic (splits x |dW| x 4 B) at ~32 MB (~25 us at the chip rate); >= 4 LDS stages
+  // per split. Deterministic mode: one split, one atomic per element.
   int splits = (512 + tiles - 1) / tiles;
   const long tile_bytes = (long)tiles * WT * WT * 4;
-  static const long atomic_mb = [] { const char* e = getenv("BIGDL_WGRAD_ATOMIC_MB"); return e ? atol(e) : 32l; }();
-  const int cap_atomic = (int)((atomic_mb << 20) / tile_bytes);
-  if (splits > cap_atomic) splits = cap_atomic;
-  const int maxsplit = (a.M + 4 * WBM - 1) / (4 * WBM);   // >= 4 LDS stages per split
-  if (splits > maxsplit) splits = maxsplit;
-  if (splits < 1 || bigdl_deterministic()) splits = 1;   // det: no workspace given -> one split, one atomic each
-  int mps = (a.M + splits - 1) / splits;
-  mps = (mps + WBM - 1) / WBM * WBM;
-  splits = (a.M + mps - 1) / mps;
-  a.m_per_split = mps;
-  a.splits = splits;
-  if (conv_impl() >= 1 && !wgrad_prefers_atomic(&a) && wgrad_g3())
-    launch_wgrad_g3(a, tiles * ((splits + 7) / 8 * 8), st);
-  else if (conv_impl() >= 1 && !wgrad_prefers_atomic(&a))
-    launch_wgrad_glds(a, tiles * ((splits + 7) / 8 * 8), st);
-  else conv_wgrad_kernel<<<dim3(tiles, splits), dim3(256), 0, st>>>(a);
+  splits = std::min(splits, (int)(((long)s.wgrad_atomic_mb << 20) / tile_bytes));
+  splits = std::min(splits, (a->M + 4 * WBM - 1) / (4 * WBM));
+  if (splits < 1 || bigdl_deterministic()) splits = 1;
+  wgrad_split(&c, a->M, splits);
+  c.kernel = !dma ? WGRAD_REG : s.wgrad_g3 ? WGRAD_G3_ATOMIC : WGRAD_GLDS_ATOMIC;
+  return c;
+}
+
+void launch_wgrad_reduce(const WgradArgs& a, int groups, hipStream_t st) {
+  const long n4 = (long)a.Ncol * a.Kdim / 4;
+  const int blocks = (int)std::min<long>((n4 + 255) / 256, 8192);
+  // groups < 0: ~2048 reduce workgroups in total, >= 4 splits per group, <= 64-way atomic contention
+  if (groups < 0)
+    groups = (blocks >= 256 || bigdl_deterministic()) ? 1 : std::max(1, std::min({2048 / blocks, a.splits / 4, 64}));
+  const dim3 grid(blocks, groups);
+  if ((reinterpret_cast<uintptr_t>(a.dw) & 15) == 0) wgrad_reduce_kernel<true><<<grid, 256, 0, st>>>(a.ws, a.dw, n4, a.splits);
+  else wgrad_reduce_kernel<false><<<grid, 256, 0, st>>>(a.ws, a.dw, n4, a.splits);
+}
+
+}  // namespace
+
+extern "C" {
+
+void bigdl_set_conv_impl(int v) { sw().impl = v; }
+void bigdl_set_conv_s1(int v) { sw().s1 = v; }
+void bigdl_set_conv_sk(int v) { sw().sk = v; }
+void bigdl_set_conv_g4(int v) { sw().g4 = v; }
+void bigdl_set_conv_shortk(int v) { sw().shortk = v; }
+void bigdl_set_conv_p8(int v) { sw().p8 = v; }
+void bigdl_set_conv_w8(int v) { sw().w8 = v; }
+void bigdl_set_wgrad_p8(int v) { sw().wgrad_p8 = v; }
+void bigdl_set_wgrad_g3(int v) { sw().wgrad_g3 = v; }
+void bigdl_set_wgrad_tr_asm(int v) { sw().wgrad_tr_asm = v; }
+int bigdl_get_conv_g4() { return sw().g4; }
+int bigdl_get_conv_impl() { return sw().impl; }
+int bigdl_get_wgrad_g3() { return sw().wgrad_g3 != 0; }
+int bigdl_get_wgrad_tr_asm() { return sw().wgrad_tr_asm != 0; }
+
+const char* bigdl_conv_kernel_name(int kernel) {
+  switch (kernel) {
+    case CONV_NONE: return "none";
+    case CONV_STEM: return "stem";
+    case CONV_G4: return "g4";
+    case CONV_S1: return "s1";
+    case CONV_HALO: return "halo";
+    case CONV_P8_SK: return "p8_sk";
+    case CONV_P8_SPLIT: return "p8_split";
+    case CONV_P8: return "p8";
+    case CONV_W8_SPLIT: return "w8_split";
+    case CONV_W8: return "w8";
+    case CONV_P3: return "p3";
+    case CONV_PERS: return "pers";
+    case CONV_GLDS_ONESTAGE: return "glds_onestage";
+    case CONV_GLDS: return "glds";
+    case CONV_GLDS_SLOWK: return "glds_slowk";
+    case CONV_REG: return "reg";
+    default: return "refused";
+  }
+}
+
+ConvChoice bigdl_conv_nt_choose(const ConvArgs* a) {
+  const ConvChoice c = conv_nt_ladder(a);
+  if (c.kernel < 0) return c;
+  // a subsampled addend and a BN applied on load only on the kernels that implement them (the caller materialises
+  // the operand otherwise): glds, p3, pers, ... would ignore the field
+  if (a->addend && (a->add_sh > 1 || a->add_sw > 1) &&
+      !(addend_stride_operands_ok(a) && (c.kernel == CONV_S1 || c.kernel == CONV_G4)))
+    return conv_choice(CONV_ERR_ADDEND);
+  if (a->pre && c.kernel != CONV_S1 && c.kernel != CONV_HALO) return conv_choice(CONV_ERR_PRE);
+  return c;
+}
+
+void bigdl_conv_addend_stride(ConvArgs* a, int sh, int sw, int add_h, int add_w) {
+  // reciprocal for q = __umulhi(x, r) == x / d, exact while x * d < 2^32 (d >= 2)
+  auto rcp = [](int d) { return d >= 2 ? (unsigned)((1ull << 32) / (unsigned)d) + 1u : 0u; };
+  const bool on = sh > 1 || sw > 1;
+  a->add_sh = on ? sh : 1; a->add_sw = on ? sw : 1;
+  a->add_H = on ? add_h : 0; a->add_W = on ? add_w : 0;
+  a->add_mow = rcp(a->OW); a->add_moh = rcp(a->OH); a->add_msh = rcp(sh); a->add_msw = rcp(sw);
+}
+
+// The subsampled addend lives in the streaming 1x1 EXT epilogue and in nt_epilogue_lds as the multi-stage tile kernel
+// calls it (identity rows)
+int bigdl_conv_addend_stride_applies(const ConvArgs* a) {
+  return (a->addend && a->add_sh > 1 && a->add_sw > 1 && bigdl_conv_nt_choose(a).kernel > 0) ? 1 : 0;
+}
+
+// Forward or data-gradient implicit GEMM: launches what bigdl_conv_nt_choose chose for `a`. Returns 0 on success, the
+// choice's refusal code, or CONV_ERR_WORKSPACE / CONV_ERR_LAUNCH.
+int bigdl_conv_nt(const ConvArgs* a, const ConvChoice* c, hipStream_t st) {
+  if (c->kernel <= 0) return c->kernel;
+  if (c->ws_floats > 0 && a->ws == nullptr) return CONV_ERR_WORKSPACE;
+  const bool n64 = c->BN == 64;
+  const bool fastk = (a->Cs % BK) == 0;
+  const int nwg256 = ((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
+  ConvArgs b;     // split kernels: ksplit from the choice
+  if (c->ws_floats > 0) {
+    b = *a;
+    b.ksplit = c->kernel == CONV_P8_SK ? c->sk_slots : c->ksplit;
+  }
+  switch (c->kernel) {
+    case CONV_STEM:
+      if (bigdl_stem_fwd(a, st) != 0) return CONV_ERR_LAUNCH;
+      break;
+    case CONV_HALO:
+      if (bigdl_conv_halo(a, st) != 0) return CONV_ERR_LAUNCH;
+      break;
+    case CONV_S1: launch_s1_any(*a, st); break;
+    case CONV_P8_SK: {
+      bigdl_fill_bytes(b.ws + (long)nwg256 * b.ksplit * 65536L, 0, (long)nwg256 * 4, st);   // tickets (a kernel: graph-safe)
+      const dim3 grid((unsigned)std::min<long>(conv_cus(), (long)nwg256 * (a->Kdim / 64)));
+      conv_nt_p8_kernel<false, false, true><<<grid, dim3(512), 0, st>>>(b);
+      break;
+    }
+    case CONV_P8_SPLIT:
+    case CONV_W8_SPLIT: {
+      const dim3 grid(nwg256, c->ksplit);
+      if (c->kernel == CONV_W8_SPLIT) conv_nt_w8_kernel<true><<<grid, dim3(512), 0, st>>>(b);
+      else if (c->ktail) conv_nt_p8_kernel<true, true><<<grid, dim3(512), 0, st>>>(b);
+      else conv_nt_p8_kernel<true><<<grid, dim3(512), 0, st>>>(b);
+      long rpb = 0;
+      const dim3 egrid = splitk_grid(a->M, a->Ncol, &rpb);
+      conv_splitk_epilogue_kernel<<<egrid, dim3(256), 0, st>>>(b, rpb);
+      break;
+    }
+    case CONV_P8:
+      if (c->ktail) conv_nt_p8_kernel<false, true><<<dim3(nwg256), dim3(512), 0, st>>>(*a);
+      else conv_nt_p8_kernel<false><<<dim3(nwg256), dim3(512), 0, st>>>(*a);
+      break;
+    case CONV_W8: conv_nt_w8_kernel<false><<<dim3(nwg256), dim3(512), 0, st>>>(*a); break;
+    case CONV_G4:
+      if (c->BM == 256) launch_nt_g4<128, 3, 256>(*a, st);
+      else if (c->stages == 2) launch_nt_g4<64, 2>(*a, st);
+      else if (c->stages == 3 && n64) launch_nt_g4<64, 3>(*a, st);
+      else if (c->stages == 3) launch_nt_g4<128, 3>(*a, st);
+      else if (n64) launch_nt_g4<64, 4>(*a, st);
+      else launch_nt_g4<128, 4>(*a, st);
+      break;
+    case CONV_P3:
+      if (n64) launch_nt_p3<64, 8, 1>(*a, st);
+      else launch_nt_p3<128, 4, 2>(*a, st);
+      break;
+    case CONV_PERS:
+      if (n64) launch_nt_pers<128, 64, 2>(*a, st);
+      else launch_nt_pers<128, 128, 2>(*a, st);
+      break;
+    case CONV_GLDS_ONESTAGE:
+      if (n64) launch_nt_glds<128, 64, 2, true, 1>(*a, st);
+      else launch_nt_glds<128, 128, 2, true, 1>(*a, st);
+      break;
+    case CONV_GLDS:
+      if (n64) launch_nt_glds<128, 64, 2>(*a, st);
+      else launch_nt_glds<128, 128, 2>(*a, st);
+      break;
+    case CONV_GLDS_SLOWK:
+      if (n64) launch_nt_glds<128, 64, 2, false>(*a, st);
+      else launch_nt_glds<128, 128, 2, false>(*a, st);
+      break;
+    case CONV_REG:
+      if (n64) launch_nt<128, 64, 2>(*a, fastk, st);
+      else launch_nt<128, 128, 2>(*a, fastk, st);
+      break;
+    default: return CONV_ERR_LAUNCH;
+  }
   HIP_LAUNCH_CHECK();
+  return 0;
+}
+
+WgradChoice bigdl_conv_wgrad_choose(const WgradArgs* a) {
+  WgradChoice c = conv_wgrad_ladder(a);
+  // dy formed on load from the consumer BN's backward: the pair-view stem kernel only; a BN applied on load: the halo
+  // kernel only (the binding materialises everything else)
+  if (a->pre_x && (a->pre || c.kernel != WGRAD_STEM)) c = WgradChoice{WGRAD_ERR_PRE_X, 0, 0, 0};
+  else if (a->pre && c.kernel != WGRAD_HALO) c = WgradChoice{WGRAD_ERR_PRE, 0, 0, 0};
+  return c;
+}
+
+// Weight gradient: launches what bigdl_conv_wgrad_choose chose for `a_in`.
+// Deterministic mode: the split kernels add their bias partials with one atomic per split, so the bias gradient is
+// taken out of them and summed by a one-row-block column sum (one atomic per channel); the weight gradient always
+// goes through the workspace partials + fixed-order reduce (no multi-split atomics, see conv_wgrad_ladder). The
+// choice was made (and its workspace sized) on the caller's args, bias gradient included.
+int bigdl_conv_wgrad(const WgradArgs* a_in, const WgradChoice* c, hipStream_t st) {
+  if (c->kernel <= 0) return c->kernel;
+  if (c->ws_floats > 0 && a_in->ws == nullptr) return WGRAD_ERR_WORKSPACE;
+  WgradArgs a = *a_in;
+  a.splits = c->splits;
+  a.m_per_split = c->m_per_split;
+  if (c->ws_floats == 0) a.ws = nullptr;
+  const bool det_bias = bigdl_deterministic() && a.dbias != nullptr && (a.ldy % 8) == 0 && a.pre_x == nullptr;
+  if (det_bias) a.dbias = nullptr;
+  const int tiles = ((a.Ncol + WT - 1) / WT) * ((a.Kdim + WT - 1) / WT);
+  const int spad = (a.splits + 7) / 8 * 8;
+  switch (c->kernel) {
+    case WGRAD_STEM: {
+      const int rc = bigdl_stem_wgrad(&a, st);
+      if (rc != 0) return rc;
+      break;
+    }
+    case WGRAD_HALO:
+      if (bigdl_wgrad_halo(&a, st) != 0) return WGRAD_ERR_LAUNCH;
+      break;
+    case WGRAD_P8_DIRECT:
+    case WGRAD_P8: {
+      const dim3 grid(((a.Ncol + 255) / 256) * ((a.Kdim + 255) / 256), a.splits);
+      const bool direct = c->kernel == WGRAD_P8_DIRECT;
+      if (sw().wgrad_tr_asm) {
+        if (direct) conv_wgrad_p8_kernel<true, true><<<grid, dim3(512), 0, st>>>(a);
+        else conv_wgrad_p8_kernel<false, true><<<grid, dim3(512), 0, st>>>(a);
+      } else {
+        if (direct) conv_wgrad_p8_kernel<true, false><<<grid, dim3(512), 0, st>>>(a);
+        else conv_wgrad_p8_kernel<false, false><<<grid, dim3(512), 0, st>>>(a);
+      }
+      if (a.splits > 1) launch_wgrad_reduce(a, 1, st);
+      break;
+    }
+    case WGRAD_GLDS_WS:
+    case WGRAD_G3_WS:
+      if (c->kernel == WGRAD_G3_WS) launch_wgrad_g3(a, tiles * spad, st);
+      else launch_wgrad_glds(a, tiles * spad, st);
+      launch_wgrad_reduce(a, -1, st);
+      break;
+    case WGRAD_GLDS_ATOMIC: launch_wgrad_glds(a, tiles * spad, st); break;
+    case WGRAD_G3_ATOMIC: launch_wgrad_g3(a, tiles * spad, st); break;
+    case WGRAD_REG: conv_wgrad_kernel<<<dim3(tiles, a.splits), dim3(256), 0, st>>>(a); break;
+    default: return WGRAD_ERR_LAUNCH;
+  }
+  HIP_LAUNCH_CHECK();
+  if (det_bias) bigdl_colsum_bf16_ld(a_in->dy, a_in->dbias, a_in->M, a_in->Ncol, a_in->ldy, st, a_in->det_ws);
   return 0;
 }
 

@@ -41,7 +41,8 @@ struct ConvArgs {
   float* out32;
   int accum32;
   // split-K (256 x 256 kernel on grids that do not fill the chip): fp32 partials [ksplit][M][Ncol] in ws, summed
-  // by the split-K epilogue kernel, which applies everything the fused epilogue would (bigdl_conv_nt_plan sets them)
+  // by the split-K epilogue kernel, which applies everything the fused epilogue would. The caller allocates ws
+  // (ConvChoice::ws_floats); bigdl_conv_nt fills ksplit from the choice
   float* ws;
   int ksplit;
   // elements between consecutive source pixels (0 = Cs). pstride < Cs views a row of small pixels as overlapping
@@ -51,7 +52,7 @@ struct ConvArgs {
   // optional [2 Cs] fp32 scale | shift of a training BatchNorm + ReLU that produced the source: the kernel reads
   // relu(x * scale[c] + shift[c]) (rounded to bf16, bit-equal to bigdl_bn_apply's output) instead of x, and zero
   // padding stays zero — the BN output is never materialised (forward GEMMs of the streaming 1x1 and halo 3x3
-  // kernels only: bigdl_conv_pre_applies)
+  // kernels only: any other choice is refused, CONV_ERR_PRE)
   const float* pre;
   // Subsampled ("compact") addend: with add_sh > 1 the addend is an [Nb][add_H][add_W][ldo] tensor at 1 / (add_sh,
   // add_sw) of the output resolution (the data gradient of a 1x1 / stride-s projection shortcut, kept at its own
@@ -75,6 +76,66 @@ struct I8Epi {
   const int8_t* add8;    // optional int8 residual addend [M][add_ld] (dequantized with add_scale, before the ReLU)
   float add_scale;
   long add_ld;
+};
+
+// Which kernel takes a ConvArgs call, and how: the one place this is decided is bigdl_conv_nt_choose. Ids <= 0 launch
+// nothing: CONV_NONE (no output rows) succeeds, the negative ones are bigdl_conv_nt's error returns.
+enum ConvKernel {
+  CONV_ERR_LAUNCH = -8,      // a launcher refused what its own predicate accepted
+  CONV_ERR_WORKSPACE = -7,   // ws_floats > 0 and no ConvArgs::ws
+  CONV_ERR_ADDEND = -6,      // subsampled addend on a kernel that does not implement it
+  CONV_ERR_PRE = -5,         // BN on load on a kernel that does not implement it
+  CONV_ERR_WINDOW = -4,      // overlapping-window source the g4 kernel cannot take
+  CONV_ERR_OUT32 = -3,
+  CONV_ERR_BNRED = -2,
+  CONV_ERR_SHAPE = -1,
+  CONV_NONE = 0,
+  CONV_STEM,                 // 7x7 / stride-2 pair-view stem (stem_fwd.hip)
+  CONV_G4,                   // multi-stage LDS-DMA tile: BM x BN, `stages` deep (2 = the short-K form)
+  CONV_S1,                   // streaming 1x1
+  CONV_HALO,                 // 3x3 from halo tiles (conv_halo.hip)
+  CONV_P8_SK,                // 256 x 256 phase-interleaved, stream-K (sk_slots slots per tile)
+  CONV_P8_SPLIT,             // ... split over K (ksplit) + split-K epilogue
+  CONV_P8,
+  CONV_W8_SPLIT,             // 256 x 256 8-wave, split over K + split-K epilogue
+  CONV_W8,
+  CONV_P3,                   // 256-pixel deep-pipelined 8-wave
+  CONV_PERS,                 // persistent LDS-DMA
+  CONV_GLDS_ONESTAGE,        // LDS-DMA, Kdim == one K-step
+  CONV_GLDS,                 // 2-stage LDS-DMA
+  CONV_GLDS_SLOWK,           // ... per-lane taps (Cs % 64 != 0)
+  CONV_REG,                  // register-staged
+};
+struct ConvChoice {
+  int kernel;                // ConvKernel
+  int BM, BN, stages;        // tile of the kernels that have several launch shapes (0 where there is one)
+  int ksplit;                // K split (1 = none)
+  int sk_slots;              // stream-K: (tile, segment) slots per tile
+  int ktail;                 // P8: one tap with Cs % 64 != 0, granules past Kdim read zeros
+  long ws_floats;            // fp32 workspace the caller passes in ConvArgs::ws (0: none)
+};
+
+// The same for the weight gradient (bigdl_conv_wgrad_choose).
+enum WgradKernel {
+  WGRAD_ERR_LAUNCH = -9,
+  WGRAD_ERR_WORKSPACE = -8,
+  WGRAD_ERR_PRE_X = -7,      // WgradArgs::pre_x on anything but the pair-view stem kernel
+  WGRAD_ERR_PRE = -6,        // WgradArgs::pre on anything but the halo kernel
+  WGRAD_ERR_SHAPE = -1,
+  WGRAD_STEM = 1,            // pair-view stem (stem_fwd.hip); splits = -1, it splits by workgroup
+  WGRAD_HALO,                // 3x3 / stride 1 from halo tiles (wgrad_halo.hip)
+  WGRAD_P8_DIRECT,           // 256 x 256 phase-interleaved, 1x1 / stride 1 operands read in place
+  WGRAD_P8,
+  WGRAD_GLDS_WS,             // 128 x 128 2-stage LDS-DMA, workspace partials + fixed-order reduce
+  WGRAD_G3_WS,               // ... 3-stage
+  WGRAD_GLDS_ATOMIC,         // the same two adding into dw with fp32 atomics
+  WGRAD_G3_ATOMIC,
+  WGRAD_REG,                 // register-staged, fp32 atomics
+};
+struct WgradChoice {
+  int kernel;                // WgradKernel
+  int splits, m_per_split;   // pixel split (WgradArgs::splits / m_per_split of the launch)
+  long ws_floats;            // fp32 workspace the caller passes in WgradArgs::ws (0: none)
 };
 
 struct WgradArgs {
@@ -109,15 +170,19 @@ void bigdl_set_deterministic(int v);
 #define BIGDL_DET_SLOTS 128
 void bigdl_colsum_bf16_ld(const uint16_t* x, float* out, long P, int K, long ld, hipStream_t st,
                           float* det_ws = nullptr);
-// 1 when bigdl_conv_nt can apply a->pre inside the kernel that takes the GEMM (else the caller materialises the source)
-int bigdl_conv_pre_applies(const ConvArgs* a);
+// Kernel choice for `a`: a pure host function of the args, the BIGDL_CONV_* switches and the device's CU count. It
+// launches nothing and tests the pointers of `a` for null / alignment only. A choice with ws_floats > 0 needs that
+// many floats in a->ws. CONV_ERR_PRE / CONV_ERR_ADDEND: no kernel that takes the GEMM applies a->pre / the subsampled
+// addend (the caller materialises the operand and chooses again).
+ConvChoice bigdl_conv_nt_choose(const ConvArgs* a);
+const char* bigdl_conv_kernel_name(int kernel);
 // Subsampled addend (ConvArgs::add_sh): bigdl_conv_addend_stride sets the stride, the addend's pixel geometry and the
-// reciprocals (sh = sw = 1 switches it off); bigdl_conv_addend_stride_applies is 1 when the kernel that bigdl_conv_nt
-// picks for `a` implements it (else the caller materialises the addend at the output resolution; bigdl_conv_nt
-// refuses such a call). Pointers of `a` are only tested for null / alignment.
+// reciprocals (sh = sw = 1 switches it off); bigdl_conv_addend_stride_applies is 1 when bigdl_conv_nt_choose accepts
+// `a` with it.
 void bigdl_conv_addend_stride(ConvArgs* a, int sh, int sw, int add_h, int add_w);
 int bigdl_conv_addend_stride_applies(const ConvArgs* a);
-int bigdl_conv_nt(const ConvArgs* a, hipStream_t st);
+// Launches the choice made for `a`; 0 on success, else a negative ConvKernel code.
+int bigdl_conv_nt(const ConvArgs* a, const ConvChoice* c, hipStream_t st);
 // 3x3 / stride-1 / pad-1 forward or data-gradient GEMM from halo tiles (conv_halo.hip)
 int bigdl_conv_halo_applies(const ConvArgs* a);
 int bigdl_conv_halo(const ConvArgs* a, hipStream_t st);
@@ -137,8 +202,6 @@ void bigdl_set_stem_fwd(int v);
 long bigdl_stem_wgrad_plan(const WgradArgs* a);
 int bigdl_stem_wgrad(const WgradArgs* a, hipStream_t st);
 void bigdl_set_stem_wgrad(int v);
-// Kernel choice for bigdl_conv_nt: sets a->ksplit and returns the fp32 workspace elements it needs (0: none).
-long bigdl_conv_nt_plan(ConvArgs* a);
 // Batched NT GEMM (bmm.hip): C[b][m][n] (=|+=) alpha * sum_k A[b][m][k] B[b][n][k]; A, B bf16 K-contiguous (K % 32
 // == 0, row strides % 8 == 0), C fp32. Returns < 0 on unsupported shapes.
 int bigdl_bmm_nt(const uint16_t* A, const uint16_t* B, float* C, int batch, int M, int N, int K, long sa, long sb,
@@ -150,10 +213,10 @@ void bigdl_pair_weight(const uint16_t* w, uint16_t* wp, int K, int C, int R, int
                        hipStream_t st);
 void bigdl_pair_wgrad_add(const float* dwp, float* gw, int K, int C, int R, int S, const long* strides, float scale,
                           hipStream_t st);
-int bigdl_conv_wgrad(const WgradArgs* a, hipStream_t st);
-// Split-K plan for the weight gradient: fills m_per_split / splits; returns the workspace size in floats
-// (0 when the single-split path accumulates straight into dw).
-long bigdl_conv_wgrad_plan(WgradArgs* a);
+// Kernel choice and pixel split for the weight gradient (a->splits / m_per_split / ws are not read), and its launch;
+// 0 on success, else a negative WgradKernel code.
+WgradChoice bigdl_conv_wgrad_choose(const WgradArgs* a);
+int bigdl_conv_wgrad(const WgradArgs* a, const WgradChoice* c, hipStream_t st);
 void bigdl_transpose_krsc(const uint16_t* w, uint16_t* wt, int K, int RS, int C, hipStream_t st);
 // batched form: desc = device int64 [n][6] {w ptr, wt ptr, K, RS, C, first tile}, tiles of 32 x 32 per (rs)
 void bigdl_transpose_krsc_batched(const long* desc, int n, int total_tiles, hipStream_t st);
@@ -303,12 +366,11 @@ int bigdl_get_conv_impl();
 void bigdl_set_conv_g4(int v);
 void bigdl_set_conv_shortk(int v);
 void bigdl_set_conv_p8(int v);
+void bigdl_set_conv_w8(int v);
 void bigdl_set_wgrad_p8(int v);
-int bigdl_conv_wgrad_uses_p8(const WgradArgs* a);
 int bigdl_get_conv_g4();
 void bigdl_set_wgrad_g3(int v);
 int bigdl_get_wgrad_g3();
-int bigdl_conv_wgrad_uses_register_kernel(const WgradArgs* a);
 void bigdl_set_wgrad_tr_asm(int v);
 int bigdl_get_wgrad_tr_asm();
 void bigdl_set_i8_g3(int v);

@@ -19,6 +19,30 @@ def _rel(a, b):
     return ((a - b).norm() / (b.norm() + 1e-12)).item()
 
 
+def _fwd_plan(case, flags=0):
+    """What conv2d_fwd runs for a (N, C, H, K, R, stride, pad) case under the current switches: conv_nt_plan_info's
+    (kernel, BM, BN, stages, ksplit, workspace floats). flags: 1 bias, 2 statistics, 4 addend, 16 / 32 consumer-BN
+    reduction (sign-mask or affine / bf16 z mask). Launches nothing."""
+    from bigdl_amd.ops import conv as cv
+    from bigdl_amd.ops import native
+
+    N, C, H, K, R, st, pd = case
+    OH = cv.out_size(H, R, st, pd)
+    return native.get().conv_nt_plan_info(cv._fwd_geo(N, H, H, C, OH, OH, st, st, R * R * C, K),
+                                          cv._fwd_taps(R, R, pd, pd, 1, 1), flags)
+
+
+def _dgrad_plans(case, flags=0):
+    """The same for conv2d_dgrad's phase GEMMs (one per stride phase)."""
+    from bigdl_amd.ops import conv as cv
+    from bigdl_amd.ops import native
+
+    N, C, H, K, R, st, pd = case
+    OH = cv.out_size(H, R, st, pd)
+    return [native.get().conv_nt_plan_info([N, OH, OH, K, nI, nJ, 1, 1, R * R * K, C, C, H, H, st, st, a, b], taps, flags)
+            for (a, b, nI, nJ, taps) in cv.dgrad_phases(H, H, R, R, (st, st), (pd, pd), (1, 1))]
+
+
 CONV_CASES = [
     # N, C, H, W, K, R, S, stride, pad
     (2, 64, 14, 14, 64, 3, 3, 1, 1),
@@ -100,6 +124,16 @@ def test_conv_nt_variants_large(case, impl):
     old = C_.get_conv_impl()
     C_.set_conv_impl(impl)
     try:
+        # the forced kernel is the one that runs: the register-staged kernel everywhere under 0; the deep-pipelined
+        # kernel on the two 100k-pixel grids under 2 (the 12544- and 6272-pixel cases have fewer than 256 of its
+        # tiles and stay on the 2-stage kernel); the persistent kernel on the two cases named for it under 3
+        reached = _fwd_plan(case, 2)[0]
+        if impl == 0:
+            assert reached == "reg"
+        if impl == 2 and case in BIG_CASES[:2]:
+            assert reached == "p3"
+        if impl == 3 and case in BIG_CASES[4:]:
+            assert reached == "pers"
         torch.manual_seed(1)
         dev = _dev()
         x = torch.randn(N, C, H, H, device=dev).to(BF, memory_format=CL)
@@ -707,7 +741,12 @@ G4_CASES = [
     (3, 40, 11, 64, 3, 2, 1),        # slow-K, BN = 64 tile, stride 2
     (8, 64, 28, 64, 1, 1, 0),        # Kdim 64, Ncol 64: the two-stage short-K variant (stages 2) in both passes
     (5, 64, 13, 40, 1, 1, 0),        # short-K, Ncol tail, M tail
+    # The streaming 1x1 and the halo 3x3 kernels now take (16, 64, 56, 256), (8, 64, 56, 64) and (8, 64, 28, 64) in
+    # both passes, so those three no longer reach this kernel (conv_nt_plan_info). The smallest cases that do:
+    (2, 64, 12, 64, 3, 1, 1),        # 3x3, BN = 64 tile, padding taps, on a width the halo kernel does not take
+    (4, 64, 14, 64, 1, 2, 0),        # Kdim 64, Ncol 64 at stride 2 (not the streaming kernel's): short-K in both passes
 ]
+G4_ELSEWHERE = [(16, 64, 56, 256, 1, 1, 0), (8, 64, 56, 64, 3, 1, 1), (8, 64, 28, 64, 1, 1, 0)]
 
 
 @pytest.mark.parametrize("stages", [4, 3, 7, 2])
@@ -726,6 +765,16 @@ def test_conv_g4_kernel_fwd_dgrad(case, stages):
     C_.set_conv_shortk(1 if stages == 2 else 0)
     try:
         N, C, H, K, R, st, pd = case
+        plans = [_fwd_plan(case, 3)] + _dgrad_plans(case, 4)
+        g4 = [p for p in plans if p[0] == "g4"]
+        assert g4 or case in G4_ELSEWHERE, plans
+        for (_, BM, BN, ns, _, _) in g4:       # the tile and the stage count the switch asks for
+            assert BM == (256 if stages == 7 and BN == 128 else 128)
+            assert ns == (4 if stages == 4 else 3) or (stages == 2 and ns == 2)
+        if stages == 2 and case == (4, 64, 14, 64, 1, 2, 0):
+            assert [p[:4] for p in plans] == [("g4", 128, 64, 2)] * 2, plans
+        if stages == 2 and case == (5, 64, 13, 40, 1, 1, 0):
+            assert plans[0][:4] == ("g4", 128, 64, 2), plans
         torch.manual_seed(7)
         dev = _dev()
         x = torch.randn(N, C, H, H, device=dev).to(BF, memory_format=CL)
@@ -749,6 +798,29 @@ def test_conv_g4_kernel_fwd_dgrad(case, stages):
     finally:
         C_.set_conv_g4(old)
         C_.set_conv_shortk(0)
+
+
+# BIGDL_CONV_W8 is off by default and had no setter, so no case above reaches the 8-wave kernel in a default run (the
+# multi-stage, streaming and halo kernels take them). The smallest cases that do under its switch:
+W8_REACH_CASES = [
+    ((2, 192, 9, 256, 1, 1, 0), ("w8", 1)),          # one tile, 6 K-steps: one pass
+    ((4, 512, 7, 2048, 1, 1, 0), ("w8_split", 2)),   # 8 tiles x 16 K-steps: split-K 2 + split-K epilogue
+]
+
+
+@pytest.mark.parametrize("case,want", W8_REACH_CASES)
+def test_conv_w8_kernel_under_its_switch(case, want):
+    from bigdl_amd.ops import native
+
+    C_ = native.get()
+    C_.set_conv_w8(1)
+    try:
+        plan = _fwd_plan(case, 3)
+        assert (plan[0], plan[4]) == want, plan
+        test_conv_w8_kernel_fwd_dgrad_bnred(case)
+        torch.cuda.synchronize()
+    finally:
+        C_.set_conv_w8(0)
 
 
 WGRAD_G3_CASES = WGRAD_CASES + [
@@ -810,7 +882,12 @@ P8_CASES = [
     (3, 64, 10, 512, 3, 1, 1),       # tiny M (one tile), Cs = 64
     (8, 200, 14, 256, 1, 1, 0),      # 1x1 with Cs % 64 != 0: one-tap K-tail mode (forward)
     (4, 256, 9, 520, 1, 1, 0),       # K-tail on the data gradient (its Cs = 520)
+    # the streaming 1x1 kernel takes the two one-pass 1x1 cases above (Kdim 256) and the halo kernel the 14 x 14 3x3
+    # one, in both passes; the smallest case that runs the full-K kernel in one pass (one tile, M tail):
+    (2, 192, 9, 256, 1, 1, 0),
 ]
+# forward kernel each case reaches under BIGDL_CONV_P8=2, in P8_CASES order (None: taken by another kernel, above)
+P8_FWD = [None, None, "p8_split", "p8_split", "p8_split", None, "p8_split", "p8", "p8", "p8"]
 
 
 @pytest.mark.parametrize("case", P8_CASES)
@@ -823,6 +900,10 @@ def test_conv_p8_kernel_fwd_dgrad(case):
     C_ = native.get()
     C_.set_conv_p8(2)
     try:
+        want = P8_FWD[P8_CASES.index(case)]
+        assert want is None or _fwd_plan(case, 3)[0] == want
+        if case == (4, 256, 9, 520, 1, 1, 0):
+            assert [p[0] for p in _dgrad_plans(case, 20)] == ["p8_split"]
         test_conv_w8_kernel_fwd_dgrad_bnred.__wrapped__(case) if hasattr(test_conv_w8_kernel_fwd_dgrad_bnred, "__wrapped__") \
             else test_conv_w8_kernel_fwd_dgrad_bnred(case)
         torch.cuda.synchronize()
@@ -915,6 +996,10 @@ def test_conv_s1_stream_kernel(case, zmask):
     for s1 in (2, 0):
         C_.set_conv_s1(s1)
         try:
+            # forward where C, data gradient where K, is 64 / 128 / 256 (a bf16 z mask is left to the tile kernels)
+            full = (N, C, H, K, 1, 1, 0)
+            assert (_fwd_plan(full, 2)[0] == "s1") == (s1 == 2 and C in (64, 128, 256))
+            assert (_dgrad_plans(full, 36 if zmask else 20)[0][0] == "s1") == (s1 == 2 and not zmask and K in (64, 128, 256))
             stats = bnops.new_stats(K, dev)
             y = cv.conv2d_fwd(x, w, None, (1, 1), (0, 0), stats=stats)
             y2 = cv.conv2d_fwd(x, w, b32, (1, 1), (0, 0), relu=True)
@@ -970,6 +1055,10 @@ SK_CASES = [
     (16, 256, 28, 256, 3, 2, 1),     # stride 2: dgrad phases with 1-4 taps
     (8, 1024, 14, 512, 1, 1, 0),     # 1x1, Ncol 512
     (3, 64, 10, 512, 3, 1, 1),       # tiny M, Cs = 64
+    # None of the five reaches the stream-K kernel any more: the halo kernel takes the first two, and the other three
+    # have fewer than 4 K-tiles per CU (tiles x K-tiles / CUs), below which the rule declines. The smallest 1x1 case
+    # that runs it in both passes (128 tiles x 8 K-tiles forward, 64 x 16 backward, 4 per CU):
+    (8, 512, 32, 1024, 1, 1, 0),
 ]
 
 
@@ -984,6 +1073,8 @@ def test_conv_p8_stream_k(case):
     C_ = native.get()
     C_.set_conv_sk(2)
     try:
+        if case == SK_CASES[-1]:
+            assert _fwd_plan(case, 3)[0] == "p8_sk" and [p[0] for p in _dgrad_plans(case, 20)] == ["p8_sk"]
         test_conv_w8_kernel_fwd_dgrad_bnred(case)
         N, C, H, K, R, st, pd = case
         torch.manual_seed(9)
