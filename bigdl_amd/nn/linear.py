@@ -400,7 +400,7 @@ class LookupTable(TensorModule):
         if self.paddingValue != 0:
             keep = keep & (idx != int(self.paddingValue) - 1)
         if self.gradWeight.is_cuda and not self.shouldScaleGradByFreq:
-            from ..ops import nnk      # fp32 atomic scatter-add straight into gradWeight
+            from ..ops import nnk      # fp32 atomic scatter-add into gradWeight (deterministic mode: sorted, in order)
 
             nnk.embedding_bwd_gpu(self.gradWeight, torch.where(keep, idx, torch.full_like(idx, -1)), g, self.scaleW)
             return

@@ -1,11 +1,14 @@
 """Fused attention on csrc/attention.hip (forward: online softmax, scores never in HBM; backward: recompute from
-the saved row max and log row sum, dQ via fp32 atomics). q / k / v: [B, H, L, D] fp32 (converted to bf16 MFMA operands),
+the saved row max and log row sum, dQ via fp32 atomics, or via the ordered no-atomics kernel in deterministic mode and
+under ``set_dq_mode("ordered")`` / BIGDL_ATTN_DQ=ordered). q / k / v: [B, H, L, D] fp32 (converted to bf16 MFMA operands),
 D = 32, 64, 96 or 128; bias broadcastable to [B, H, Lq, Lk] or a causal mask; attention dropout (reference
 S/nn/Attention.scala:59 ``attentionDropout``) in-kernel: the keep mask is a counter-based hash of (seed, row, key)
 that the backward regenerates, so nothing of size Lq x Lk is ever stored (``dropout_mask`` reproduces it on the
 host for tests).
 
 The bias is treated as a constant (attention masks): its gradient is not produced by the fused path."""
+import os
+
 import torch
 
 from . import native
@@ -31,6 +34,26 @@ def dropout_mask(seed, BH, Lq, Lk, p):
     thr = min(int(p * 4294967296.0), 4294967295) if p > 0 else 0
     keep = (h >= max(thr, 1 if p > 0 else 0)).float()
     return keep / (1.0 - p) if p > 0 else keep
+
+
+_DQ_MODES = {None: -1, "atomic": 0, "ordered": 1}
+
+
+def set_dq_mode(mode):
+    """dQ route of the fused backward: "atomic" (fp32 atomics over key blocks, the default), "ordered" (one workgroup
+    per query block sums the key blocks in order: bitwise reproducible, one more S / P / dP recomputation) or None
+    (back to BIGDL_ATTN_DQ / the default). Deterministic mode takes the ordered kernel whatever is set here."""
+    if mode not in _DQ_MODES:
+        raise ValueError(f"set_dq_mode: {mode!r} is not one of 'atomic', 'ordered', None")
+    if mode is None:
+        mode = os.environ.get("BIGDL_ATTN_DQ") or None
+        mode = mode if mode is None or mode == "ordered" else "atomic"      # the native reading of the variable
+    native.get().set_attn_dq(_DQ_MODES[mode])
+
+
+def dq_route():
+    """The dQ kernel the next backward takes: "ordered" or "atomic"."""
+    return "ordered" if native.get().attn_dq_ordered() else "atomic"
 
 
 class _FlashAttention(torch.autograd.Function):
@@ -63,11 +86,13 @@ class _FlashAttention(torch.autograd.Function):
         q16, k16, v16, o, mlog = ctx.saved_tensors
         B, H, Lq, Lk, D = ctx.shape
         do = do.reshape(B * H, Lq, D).float().contiguous()
-        dq = torch.zeros(B * H, Lq, D, device=do.device)
+        mod = native.get()
+        # the ordered dQ kernel stores every element; the atomic one accumulates into zeros
+        dq = (torch.empty if mod.attn_dq_ordered() else torch.zeros)(B * H, Lq, D, device=do.device)
         dk = torch.empty(B * H, Lk, D, device=do.device)
         dv = torch.empty(B * H, Lk, D, device=do.device)
         delta = torch.empty(B * H, Lq, device=do.device)
-        native.get().attn_bwd(q16, k16, v16, ctx.bias, ctx.H, ctx.causal, o, mlog, do, dq, dk, dv, delta,
+        mod.attn_bwd(q16, k16, v16, ctx.bias, ctx.H, ctx.causal, o, mlog, do, dq, dk, dv, delta,
                               ctx.drop[0], ctx.drop[1])
         return dq.view(B, H, Lq, D), dk.view(B, H, Lk, D), dv.view(B, H, Lk, D), None, None, None, None
 

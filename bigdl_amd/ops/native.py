@@ -83,7 +83,12 @@ def deterministic():
     """Deterministic mode (``bigdl.deterministic`` / BIGDL_DETERMINISTIC=1): every GPU reduction that would land
     through float atomics from several workgroups runs in a fixed order instead (BN statistics and backward sums in
     one-writer slots outside the GEMM epilogues, weight gradients through workspace partials + a fixed-order reduce,
-    bias gradients, loss and norms in one row block), so two training runs from the same seed are bitwise equal.
+    bias gradients and norms in one row block, the cross-entropy loss from per-block partials added in a fixed
+    order), so two training runs from the same seed are bitwise equal.
+    On the Transformer path: attention dQ comes from the ordered kernel (one workgroup per query block, key blocks
+    in order, plain stores; csrc/attention.hip), LayerNorm's dgamma / dbeta from per-chunk partials summed in chunk
+    order, and the embedding gradient from a stable sort of the ids and one in-order sum per weight row.
+    Still atomic in this mode: Tensor indexAdd / scatter (csrc/index_ops.hip) and resize_bilinear's backward.
     Costs speed (tools/det_check.py records how much)."""
     return _DET[0]
 

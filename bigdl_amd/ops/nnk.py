@@ -60,12 +60,19 @@ def lrn(x, size, alpha, beta, k):
 
 
 # ---------------------------------------------------------------------------------------------- dropout
-_seed_counter = [0x5EED]
+_SEED_COUNTER0 = 0x5EED
+_seed_counter = [_SEED_COUNTER0]
+_seed_epoch = [None]
 
 
 def next_seed():
+    """Seed of the next dropout mask: high half from the framework RNG, low half a call counter that restarts with
+    every RNG.setSeed, so a second run in the same process after the same setSeed draws the same masks."""
     from ..utils.random_generator import RNG
 
+    if _seed_epoch[0] != RNG.seedings:
+        _seed_epoch[0] = RNG.seedings
+        _seed_counter[0] = _SEED_COUNTER0
     _seed_counter[0] += 1
     return ((RNG.random() & 0x7FFFFFFF) << 32) | (_seed_counter[0] & 0xFFFFFFFF)     # deterministic under RNG.setSeed
 
@@ -89,6 +96,8 @@ def embedding_fwd_gpu(weight, idx):
 
 
 def embedding_bwd_gpu(grad_weight, idx, gout, scale=1.0):
+    """grad_weight[idx] += scale * gout (negative idx skipped): fp32 atomics, or in deterministic mode a stable sort
+    of idx and one in-order sum per weight row (the binding routes on the mode)."""
     native.get().embedding_bwd(gout.contiguous().float(), idx.contiguous(), grad_weight, float(scale))
 
 

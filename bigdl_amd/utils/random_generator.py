@@ -17,6 +17,7 @@ class RandomGenerator:
 
     def setSeed(self, seed):
         self._seed = int(seed)
+        self.seedings = getattr(self, "seedings", 0) + 1     # streams derived from this one restart with it (nnk.next_seed)
         self._gen.manual_seed(self._seed)
         torch.manual_seed(self._seed)
         return self

@@ -17,6 +17,15 @@
 // Backward (one workgroup per 64-key block, looping over query blocks): P is recomputed from the saved
 // row max and log l (P = exp((S - m) - log l)); dV += P^T dO, dP = dO V^T, dS = P (dP - rowsum(dO o O)),
 // dK += dS^T Q accumulate in VGPRs; dQ += dS K is accumulated across key blocks with fp32 atomics.
+// Ordered dQ (deterministic mode, or BIGDL_ATTN_DQ=ordered): the key-block kernel is instantiated without its dQ part
+// and attn_dq_kernel computes dQ in the forward's shape: one workgroup per 64 query rows, Q and dO fragments in
+// VGPRs, K / K^T / V streamed through LDS in ascending key-block order, S, P, dP and dS recomputed per tile with the
+// same roundings (P fp32, dS bf16 before the MFMA), dQ accumulated in fp32 registers over all tiles and stored once
+// with plain stores: no atomics, no dependence on dq's previous contents, bitwise reproducible. It costs one more
+// recomputation of S / P / dP (tools/attn_dq_ab.py times both routes).
+#include <stdlib.h>
+#include <string.h>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -222,7 +231,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
 // 64-row query block: S^T = K Q^T (per wave 16 keys x 64 q), P^T = exp(S^T + bias - lse), dP^T = V dO^T,
 // dS^T = P^T (dP^T - delta); dV += P^T dO, dK += dS^T Q (A operands through the wave's LDS slice, B operands from
 // transposed dO / Q tiles), dQ += dS K via fp32 atomics (dS gathered in LDS [q][key], K^T tile as B operand).
-template <int D>
+// DQ = false: everything but the dQ part (the ordered route, where attn_dq_kernel owns dq).
+template <int D, bool DQ>
 __global__ void __launch_bounds__(256) attn_bwd_kernel(AttnArgs a) {
   constexpr int KS = D / 32, NC = D / 16;
   __shared__ __attribute__((aligned(16))) bf16_t sQ[AT_BK * D];      // Q block, row-major [q][d]
@@ -251,7 +261,7 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(AttnArgs a) {
       vf[s] = kr < a.Lk ? *reinterpret_cast<const v8s*>(V + (long)kr * D + 32 * s + 8 * grp) : z;
     }
   }
-  stage<D>(K, k0, a.Lk, nullptr, sKt);
+  if constexpr (DQ) stage<D>(K, k0, a.Lk, nullptr, sKt);
   v4f dk[NC], dv[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) { dk[c] = v4f{0.f, 0.f, 0.f, 0.f}; dv[c] = v4f{0.f, 0.f, 0.f, 0.f}; }
@@ -330,7 +340,7 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(AttnArgs a) {
         const float ds = st[j][i] * (dpt[j][i] * dm[j][i] - sDel[16 * j + col]);
         const bf16_t d16 = f2bf(ds);
         T[(4 * grp + i) * AT_BK + 16 * j + col] = d16;
-        sdS[(16 * j + col) * AT_BK + wave * 16 + 4 * grp + i] = d16;
+        if constexpr (DQ) sdS[(16 * j + col) * AT_BK + wave * 16 + 4 * grp + i] = d16;
       }
     }
     __syncthreads();
@@ -341,17 +351,19 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(AttnArgs a) {
       for (int c = 0; c < NC; ++c) dk[c] = mfma(df, lds8(sQt + (16 * c + col) * AT_BK + 32 * t + 8 * grp), dk[c]);
     }
     // dQ[q0 + 16 w + ..][:] += dS[q rows of this wave][64 keys] . K[64 keys][:]
+    if constexpr (DQ) {
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      v4f acc = {0.f, 0.f, 0.f, 0.f};
+      for (int c = 0; c < NC; ++c) {
+        v4f acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int t = 0; t < AT_BK / 32; ++t)
-        acc = mfma(lds8(sdS + (wave * 16 + col) * AT_BK + 32 * t + 8 * grp),
-                   lds8(sKt + (16 * c + col) * AT_BK + 32 * t + 8 * grp), acc);
+        for (int t = 0; t < AT_BK / 32; ++t)
+          acc = mfma(lds8(sdS + (wave * 16 + col) * AT_BK + 32 * t + 8 * grp),
+                     lds8(sKt + (16 * c + col) * AT_BK + 32 * t + 8 * grp), acc);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int qi = q0 + wave * 16 + 4 * grp + i;
-        if (qi < a.Lq) atomicAdd(a.dq + ((long)bh * a.Lq + qi) * D + 16 * c + col, acc[i]);
+        for (int i = 0; i < 4; ++i) {
+          const int qi = q0 + wave * 16 + 4 * grp + i;
+          if (qi < a.Lq) atomicAdd(a.dq + ((long)bh * a.Lq + qi) * D + 16 * c + col, acc[i]);
+        }
       }
     }
   }
@@ -365,6 +377,112 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(AttnArgs a) {
       a.dk[((long)bh * a.Lk + kj) * D + 16 * c + col] = dk[c][i];
       a.dv[((long)bh * a.Lk + kj) * D + 16 * c + col] = dv[c][i];
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------- ordered dQ
+// Workgroup = 64 query rows (4 waves x 16) of one (batch, head), key tiles in ascending order. Per tile and wave:
+// S = Q K^T and dP = dO V^T (Q / dO fragments from VGPRs against the row-major K / V tiles), P from the saved row max
+// and log l, dS = P (dP dm - delta) rounded to bf16 into the wave's LDS slice [16 q][64 keys] (accumulator layout ->
+// A-operand layout), dQ += dS K against the K^T tile. Causal: key blocks k0 <= the block's first query row only
+// (top-left aligned, the mirror of attn_bwd_kernel's qstart), kj > qi inside a block.
+template <int D>
+__global__ void __launch_bounds__(256) attn_dq_kernel(AttnArgs a) {
+  constexpr int KS = D / 32, NC = D / 16;
+  __shared__ __attribute__((aligned(16))) bf16_t sK[AT_BK * D];      // K tile row-major [key][d]
+  __shared__ __attribute__((aligned(16))) bf16_t sKt[D * AT_BK];     // K^T [d][key]
+  __shared__ __attribute__((aligned(16))) bf16_t sV[AT_BK * D];      // V tile row-major
+  __shared__ __attribute__((aligned(16))) bf16_t sS[4][16 * AT_BK];  // per-wave dS slice
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int grp = lane >> 4, col = lane & 15;
+  const int bh = blockIdx.y;
+  const int q0 = blockIdx.x * AT_BQ + wave * 16;   // this wave's first query row
+  const bf16_t* Q = a.q + (long)bh * a.Lq * D;
+  const bf16_t* K = a.k + (long)bh * a.Lk * D;
+  const bf16_t* V = a.v + (long)bh * a.Lk * D;
+  const float* dO = a.dout + (long)bh * a.Lq * D;
+  // Q and dO fragments (A operands): row q0 + col, k = 32 s + 8 grp; dO fp32 rounded to bf16 on load
+  v8s qf[KS], dof[KS];
+  {
+    const int qr = q0 + col;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      v8s z = {0, 0, 0, 0, 0, 0, 0, 0};
+      qf[s] = z;
+      dof[s] = z;
+      if (qr < a.Lq) {
+        qf[s] = *reinterpret_cast<const v8s*>(Q + (long)qr * D + 32 * s + 8 * grp);
+        const v4f lo = *reinterpret_cast<const v4f*>(dO + (long)qr * D + 32 * s + 8 * grp);
+        const v4f hi = *reinterpret_cast<const v4f*>(dO + (long)qr * D + 32 * s + 8 * grp + 4);
+        v4u pk;
+        pk[0] = pack2bf(lo[0], lo[1]); pk[1] = pack2bf(lo[2], lo[3]);
+        pk[2] = pack2bf(hi[0], hi[1]); pk[3] = pack2bf(hi[2], hi[3]);
+        dof[s] = __builtin_bit_cast(v8s, pk);
+      }
+    }
+  }
+  // row max, log l, delta and dropout row hash of rows q0 + 4 grp + i
+  float rm[4], rl[4], rdel[4];
+  unsigned rrow[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int qi = q0 + 4 * grp + i;
+    const bool live = qi < a.Lq;
+    rm[i] = live ? a.mlog[(long)bh * a.Lq + qi] : 0.f;
+    rl[i] = live ? a.mlog[((long)gridDim.y + bh) * a.Lq + qi] : 0.f;
+    rdel[i] = live ? a.delta[(long)bh * a.Lq + qi] : 0.f;
+    rrow[i] = a.drop_thr ? drop_row(a, bh, qi) : 0u;
+  }
+  v4f dq[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) dq[c] = v4f{0.f, 0.f, 0.f, 0.f};
+  int kend = a.Lk;
+  if (a.causal) {
+    const int qlast = blockIdx.x * AT_BQ + AT_BQ - 1;
+    kend = qlast + 1 < a.Lk ? qlast + 1 : a.Lk;
+  }
+  bf16_t* T = sS[wave];
+  for (int k0 = 0; k0 < kend; k0 += AT_BK) {
+    __syncthreads();                              // previous tile's sK / sKt / sV / sS reads are done
+    stage<D>(K, k0, a.Lk, sK, sKt);
+    stage<D>(V, k0, a.Lk, sV, nullptr);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v4f s_acc = {0.f, 0.f, 0.f, 0.f}, p_acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        s_acc = mfma(qf[s], lds8(sK + (16 * j + col) * D + 32 * s + 8 * grp), s_acc);
+        p_acc = mfma(dof[s], lds8(sV + (16 * j + col) * D + 32 * s + 8 * grp), p_acc);
+      }
+      // s_acc[i] = S[q0 + 4 grp + i][k0 + 16 j + col], p_acc[i] = (dO V^T) likewise
+      const int kj = k0 + 16 * j + col;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int qi = q0 + 4 * grp + i;
+        float p = 0.f;
+        if (qi < a.Lq && kj < a.Lk && !(a.causal && kj > qi))
+          p = __expf((s_acc[i] + bias_at(a, bh, qi, kj) - rm[i]) - rl[i]);
+        const float dm = a.drop_thr ? drop_mul(a, rrow[i], kj) : 1.f;
+        const float ds = p * (p_acc[i] * dm - rdel[i]);
+        T[(4 * grp + i) * AT_BK + 16 * j + col] = f2bf(ds);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < AT_BK / 32; ++t) {
+      const v8s df = lds8(T + col * AT_BK + 32 * t + 8 * grp);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) dq[c] = mfma(df, lds8(sKt + (16 * c + col) * AT_BK + 32 * t + 8 * grp), dq[c]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int qi = q0 + 4 * grp + i;
+    if (qi >= a.Lq) continue;
+    float* row = a.dq + ((long)bh * a.Lq + qi) * D;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) row[16 * c + col] = dq[c][i];
   }
 }
 
@@ -417,12 +535,34 @@ int bigdl_attn_bwd(const AttnCall* c, float* delta_ws, hipStream_t st) {
   AttnArgs a = to_args(c);
   a.delta = delta_ws;
   dim3 grid((c->Lk + AT_BK - 1) / AT_BK, c->BH);
+  if (!bigdl_attn_dq_ordered()) {
+    switch (c->D) {
+      case 32: attn_bwd_kernel<32, true><<<grid, 256, 0, st>>>(a); break;
+      case 64: attn_bwd_kernel<64, true><<<grid, 256, 0, st>>>(a); break;
+      case 96: attn_bwd_kernel<96, true><<<grid, 256, 0, st>>>(a); break;
+      default: attn_bwd_kernel<128, true><<<grid, 256, 0, st>>>(a); break;
+    }
+    HIP_LAUNCH_CHECK();
+    return 0;
+  }
+  dim3 qgrid((c->Lq + AT_BQ - 1) / AT_BQ, c->BH);
   switch (c->D) {
-    case 32: attn_bwd_kernel<32><<<grid, 256, 0, st>>>(a); break;
-    case 64: attn_bwd_kernel<64><<<grid, 256, 0, st>>>(a); break;
-    case 96: attn_bwd_kernel<96><<<grid, 256, 0, st>>>(a); break;
-    default: attn_bwd_kernel<128><<<grid, 256, 0, st>>>(a); break;
+    case 32: attn_bwd_kernel<32, false><<<grid, 256, 0, st>>>(a); attn_dq_kernel<32><<<qgrid, 256, 0, st>>>(a); break;
+    case 64: attn_bwd_kernel<64, false><<<grid, 256, 0, st>>>(a); attn_dq_kernel<64><<<qgrid, 256, 0, st>>>(a); break;
+    case 96: attn_bwd_kernel<96, false><<<grid, 256, 0, st>>>(a); attn_dq_kernel<96><<<qgrid, 256, 0, st>>>(a); break;
+    default: attn_bwd_kernel<128, false><<<grid, 256, 0, st>>>(a); attn_dq_kernel<128><<<qgrid, 256, 0, st>>>(a); break;
   }
   HIP_LAUNCH_CHECK();
   return 0;
+}
+
+// dQ route: BIGDL_ATTN_DQ=atomic|ordered (unset: atomic); deterministic mode always takes the ordered kernel.
+static int g_attn_dq = -2;   // -2: environment not read yet, -1 unset, 0 atomic, 1 ordered
+void bigdl_set_attn_dq(int v) { g_attn_dq = v < 0 ? -1 : (v ? 1 : 0); }
+int bigdl_attn_dq_ordered() {
+  if (g_attn_dq == -2) {
+    const char* e = getenv("BIGDL_ATTN_DQ");
+    g_attn_dq = !e || !*e ? -1 : (strcmp(e, "ordered") == 0 ? 1 : 0);
+  }
+  return (bigdl_deterministic() || g_attn_dq == 1) ? 1 : 0;
 }

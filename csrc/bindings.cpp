@@ -719,8 +719,11 @@ void softmax_xent(const Tensor& logits, const Tensor& labels, const OptT& loss, 
     TORCH_CHECK(dlogits->numel() == logits.numel(), "softmax_xent: dlogits");
     if (dlogits->scalar_type() == at::kBFloat16) db = mbf(*dlogits, "dlogits"); else df = mf(*dlogits, "dlogits");
   }
+  Tensor ws;      // deterministic mode: one slot per block for the loss partials, added in a fixed order
+  if (bigdl_deterministic() && loss && loss->defined())
+    ws = at::empty({BIGDL_XENT_SLOTS}, logits.options().dtype(at::kFloat));
   bigdl_softmax_xent(lb, lf, cf(labels, "labels"), omf(loss, "loss"), db, df, B, K, (float)label_base,
-                     (float)grad_scale, stream());
+                     (float)grad_scale, stream(), ws.defined() ? ws.data_ptr<float>() : nullptr);
 }
 
 void sgd_step(const Tensor& w, const Tensor& g, const OptT& mom, const OptT& w16, double lr, double wd,
@@ -1228,10 +1231,24 @@ void embedding_fwd(const Tensor& W, const Tensor& idx, const Tensor& out) {
   bigdl_embedding_fwd(cf(W, "W"), (const long*)idx.data_ptr(), mf(out, "out"), idx.numel(), W.size(1), W.size(0),
                       stream());
 }
+// Deterministic mode: group the token positions by weight row with a stable sort (positions stay ascending inside a
+// row's run) and reduce every run in that order (csrc/nn_misc.hip, embedding_bwd_sorted_kernel): no atomics.
+void embedding_bwd_sorted(const Tensor& gout, const Tensor& keys, const Tensor& gW, double scale) {
+  auto sorted = at::sort(keys, /*stable=*/true, /*dim=*/0, /*descending=*/false);
+  const Tensor ks = std::get<0>(sorted).contiguous(), pos = std::get<1>(sorted).contiguous();
+  bigdl_embedding_bwd_sorted(gout.data_ptr(), gout.scalar_type() == at::kBFloat16 ? 1 : 0, (const long*)ks.data_ptr(),
+                             (const long*)pos.data_ptr(), mf(gW, "gW"), ks.numel(), gW.size(1), gW.size(0),
+                             (float)scale, stream());
+}
 void embedding_bwd(const Tensor& gout, const Tensor& idx, const Tensor& gW, double scale) {
   contig(gout, "gout"); contig(idx, "idx"); contig(gW, "gW");
   TORCH_CHECK(gW.dim() == 2 && idx.scalar_type() == at::kLong && idx.is_cuda(), "embedding_bwd: gW 2-D, idx int64");
   TORCH_CHECK(gout.numel() == idx.numel() * gW.size(1), "embedding_bwd: gout size");
+  if (bigdl_deterministic()) {
+    cf(gout, "gout");
+    embedding_bwd_sorted(gout, idx.reshape({-1}), gW, scale);
+    return;
+  }
   bigdl_embedding_bwd(cf(gout, "gout"), (const long*)idx.data_ptr(), mf(gW, "gW"), idx.numel(), gW.size(1), gW.size(0),
                       scale, stream());
 }
@@ -1250,6 +1267,12 @@ void embedding_bwd_ids(const Tensor& gout, const Tensor& ids, const Tensor& gW, 
   TORCH_CHECK(gW.dim() == 2 && ids.is_cuda() && (il || ids.scalar_type() == at::kFloat), "embedding_bwd_ids: ids f32/i64");
   TORCH_CHECK(gb || gout.scalar_type() == at::kFloat, "embedding_bwd_ids: gout f32 or bf16");
   TORCH_CHECK(gout.numel() == ids.numel() * gW.size(1), "embedding_bwd_ids: gout size");
+  if (bigdl_deterministic()) {
+    Tensor k = ids.reshape({-1}).to(at::kLong) - 1;      // the kernels' (long)id - 1; a negative key is skipped
+    if (pad >= 0) k = k.masked_fill(k.eq(pad), -1);
+    embedding_bwd_sorted(gout, k, gW, scale);
+    return;
+  }
   bigdl_embedding_bwd_ids(gout.data_ptr(), gb ? 1 : 0, ids.data_ptr(), il ? 1 : 0, mf(gW, "gW"), ids.numel(), gW.size(1),
                           gW.size(0), pad, (float)scale, stream());
 }
@@ -1513,8 +1536,14 @@ void layernorm_bwd(const Tensor& dy, const Tensor& x, const OptT& g, const Tenso
   if (g && g->defined()) TORCH_CHECK(g->numel() == D && g->is_contiguous(), "layernorm_bwd: gamma");
   if (dg && dg->defined()) TORCH_CHECK(dg->numel() == D && dg->is_contiguous(), "layernorm_bwd: dgamma");
   if (db && db->defined()) TORCH_CHECK(db->numel() == D && db->is_contiguous(), "layernorm_bwd: dbeta");
+  // deterministic mode: the row chunks' partial sums go to a workspace [chunks][2][D] and are added in chunk order
+  Tensor ws;
+  const bool params = (dg && dg->defined()) || (db && db->defined());
+  if (bigdl_deterministic() && params)
+    ws = at::empty({bigdl_layernorm_param_chunks(rows, (int)D) * 2 * D}, x.options().dtype(at::kFloat));
   TORCH_CHECK(bigdl_layernorm_bwd(cf(dy, "dy"), cf(x, "x"), ocf(g, "g"), cf(mean, "mean"), cf(rstd, "rstd"),
-                                  omf(dx, "dx"), omf(dg, "dg"), omf(db, "db"), rows, (int)D, stream()) == 0,
+                                  omf(dx, "dx"), omf(dg, "dg"), omf(db, "db"), rows, (int)D,
+                                  ws.defined() ? ws.data_ptr<float>() : nullptr, stream()) == 0,
               "layernorm_bwd: hidden size > 4096");
 }
 AttnCall attn_call(const Tensor& q, const Tensor& k, const Tensor& v, const OptT& bias, int64_t H, bool causal) {
@@ -1871,6 +1900,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("causal"), py::arg("o"), py::arg("mlog"), py::arg("dout"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
         py::arg("delta_ws"), py::arg("drop_p") = 0.0, py::arg("seed") = 0);
   m.def("layernorm_bwd", &layernorm_bwd);
+  m.def("set_attn_dq", &bigdl_set_attn_dq, "attention dQ route: -1 unset (BIGDL_ATTN_DQ decides), 0 atomic, 1 ordered");
+  m.def("attn_dq_ordered", &bigdl_attn_dq_ordered, "1 if the next attn_bwd takes the ordered (no-atomics) dQ kernel");
   m.def("gru_step", &gru_step, py::arg("mode"), py::arg("A"), py::arg("W"), py::arg("B"), py::arg("H"),
         py::arg("xg") = py::none(), py::arg("hprev") = py::none(), py::arg("r") = py::none(), py::arg("z") = py::none(),
         py::arg("n") = py::none(), py::arg("rh16") = py::none(), py::arg("hout") = py::none(),

@@ -540,7 +540,8 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void softmax_xent_kernel(const bf16_t* __restrict__ lb, const float* __restrict__ lf,
                                                            const float* __restrict__ labels, float* __restrict__ loss,
                                                            bf16_t* __restrict__ db, float* __restrict__ df, int B, int K,
-                                                           float label_base, float grad_scale) {
+                                                           float label_base, float grad_scale,
+                                                           float* __restrict__ loss_slots) {
   __shared__ float part[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float my_loss = 0.f;
@@ -618,8 +619,21 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const bf16_t* __restr
   if (loss) {
     if (lane == 0) part[wave] = my_loss;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss, part[0] + part[1] + part[2] + part[3]);
+    if (threadIdx.x == 0) {
+      const float s = part[0] + part[1] + part[2] + part[3];
+      if (loss_slots) loss_slots[blockIdx.x] = s;     // deterministic mode: softmax_xent_finish_kernel adds them up
+      else atomicAdd(loss, s);
+    }
   }
+}
+
+// Deterministic mode: loss += the blocks' partials in a fixed order (lane l takes slots l, l + 64, ..., then the
+// wave's xor-shuffle tree).
+__global__ void softmax_xent_finish_kernel(const float* __restrict__ slots, int n, float* __restrict__ loss) {
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 64) s += slots[i];
+  s = wave_sum(s);
+  if (threadIdx.x == 0) *loss += s;
 }
 
 // ---------------- optimizers on flat fp32 buffers ----------------
@@ -1030,13 +1044,17 @@ void bigdl_avgpool_bwd(const uint16_t* dy, uint16_t* dx, int N, int H, int W, in
   HIP_LAUNCH_CHECK();
 }
 void bigdl_softmax_xent(const uint16_t* lb, const float* lf, const float* labels, float* loss, uint16_t* db, float* df,
-                        int B, int K, float label_base, float grad_scale, hipStream_t st) {
-  const int blocks = bigdl_deterministic() ? 1 : std::min((B + 3) / 4, 2048);   // det: one loss atomic
+                        int B, int K, float label_base, float grad_scale, hipStream_t st, float* det_ws) {
+  // deterministic mode: the blocks' loss partials go to det_ws slots and are added in a fixed order; without a
+  // workspace (or without a loss) one block, hence one loss atomic
+  float* slots = bigdl_deterministic() && loss ? det_ws : nullptr;
+  const int blocks = bigdl_deterministic() && loss && !slots ? 1 : std::min((B + 3) / 4, BIGDL_XENT_SLOTS);
   const bool vec = lb ? (K % 8 == 0) : (K % 4 == 0);   // rows start 16-byte aligned when K is a multiple
   if (vec)
-    softmax_xent_kernel<true><<<blocks, 256, 0, st>>>(lb, lf, labels, loss, db, df, B, K, label_base, grad_scale);
+    softmax_xent_kernel<true><<<blocks, 256, 0, st>>>(lb, lf, labels, loss, db, df, B, K, label_base, grad_scale, slots);
   else
-    softmax_xent_kernel<false><<<blocks, 256, 0, st>>>(lb, lf, labels, loss, db, df, B, K, label_base, grad_scale);
+    softmax_xent_kernel<false><<<blocks, 256, 0, st>>>(lb, lf, labels, loss, db, df, B, K, label_base, grad_scale, slots);
+  if (slots) softmax_xent_finish_kernel<<<1, 64, 0, st>>>(slots, blocks, loss);
   HIP_LAUNCH_CHECK();
 }
 void bigdl_sgd_step(float* w, const float* g, float* mom, uint16_t* w16, long n, const float* lr_dev, float lr,

@@ -288,7 +288,10 @@ void bigdl_avgpool_bwd(const uint16_t* dy, uint16_t* dx, int N, int H, int W, in
 // fused log-softmax + NLL (cross entropy) over rows of logits
 void bigdl_softmax_xent(const uint16_t* logits_bf16, const float* logits_f32, const float* labels,
                         float* loss, uint16_t* dlogits_bf16, float* dlogits_f32, int B, int K,
-                        float label_base, float grad_scale, hipStream_t st);
+                        float label_base, float grad_scale, hipStream_t st, float* det_ws = nullptr);
+// Deterministic mode with det_ws (BIGDL_XENT_SLOTS floats): the usual grid, every block stores its loss partial to its
+// own slot and one wave adds the slots in a fixed order; without det_ws the whole batch runs in one block.
+#define BIGDL_XENT_SLOTS 2048
 
 // optimizers over flat fp32 buffers (optional bf16 shadow written in the same pass)
 void bigdl_sgd_step(float* w, const float* g, float* mom, uint16_t* w16, long n, const float* lr_dev, float lr,
@@ -417,6 +420,11 @@ void bigdl_embedding_bwd_ids(const void* gout, int gout_bf16, const void* ids, i
                              long nIndex, long pad, float scale, hipStream_t st);
 void bigdl_embedding_bwd(const float* gout, const long* idx, float* gW, long rows, int D, long nIndex, float scale,
                          hipStream_t st);
+// Deterministic-mode embedding gradient: keys = the weight row of every token position, stably sorted (ascending
+// position inside a row's run), pos = the matching positions. Every run whose key lies in [0, nIndex) is summed in
+// fp32 in that order, one wave per (run, 64-column slice), then gW[key] += scale * sum once. No atomics.
+void bigdl_embedding_bwd_sorted(const void* gout, int gout_bf16, const long* keys, const long* pos, float* gW, long rows,
+                                int D, long nIndex, float scale, hipStream_t st);
 void bigdl_resize_bilinear_fwd(const float* x, float* y, long NC, int H, int W, int OH, int OW, float sh, float sw,
                                hipStream_t st);
 void bigdl_resize_bilinear_bwd(const float* gy, float* gx, long NC, int H, int W, int OH, int OW, float sh, float sw,
@@ -484,7 +492,10 @@ int bigdl_gru_step(const GruStepArgs* a, hipStream_t st);
 int bigdl_layernorm_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, long rows,
                         int D, float eps, hipStream_t st);
 int bigdl_layernorm_bwd(const float* dy, const float* x, const float* g, const float* mean, const float* rstd,
-                        float* dx, float* dg, float* db, long rows, int D, hipStream_t st);
+                        float* dx, float* dg, float* db, long rows, int D, float* det_ws, hipStream_t st);
+// Row chunks of the parameter-gradient pass, a function of (rows, D) only. In deterministic mode the caller passes
+// det_ws, chunks x 2 x D floats: every chunk stores its partial sums there and one pass adds them up in chunk order.
+long bigdl_layernorm_param_chunks(long rows, int D);
 
 // Fused attention (csrc/attention.hip). q/k/v bf16 [BH][L][D] (D = 32, 64, 96 or 128), bias fp32 through element
 // strides (sb, sh, sq, sk) or nullptr, o / dq / dk / dv / dout fp32, lse / delta fp32 [BH][Lq] (lse is an output only); attention dropout
@@ -498,6 +509,11 @@ typedef struct {
 } AttnCall;
 int bigdl_attn_fwd(const AttnCall* c, hipStream_t st);
 int bigdl_attn_bwd(const AttnCall* c, float* delta_ws, hipStream_t st);
+// dQ route of bigdl_attn_bwd (BIGDL_ATTN_DQ=atomic|ordered): -1 unset, 0 atomic, 1 ordered. Unset and atomic mean the
+// fp32-atomic sum over key blocks, except in deterministic mode, which always takes the ordered kernel. The ordered
+// kernel overwrites dq (no zero fill needed). bigdl_attn_dq_ordered(): 1 if the next call takes the ordered kernel.
+void bigdl_set_attn_dq(int v);
+int bigdl_attn_dq_ordered();
 
 // Single-token attention decode and KV-cache maintenance (csrc/attn_decode.hip). q / o fp32 [N][heads * D] (q already
 // scaled; rounded to bf16 on load), kcache / vcache bf16 [R][Lmax][heads * D], keys 0..len-1 valid, rows (optional,

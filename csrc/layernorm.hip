@@ -90,7 +90,8 @@ __global__ void __launch_bounds__(LN_THREADS) ln_bwd_kernel(const float* __restr
 __global__ void __launch_bounds__(LN_THREADS) ln_param_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                               const float* __restrict__ mean,
                                                               const float* __restrict__ rstd, float* __restrict__ dg,
-                                                              float* __restrict__ db, long rows, int D, long chunk) {
+                                                              float* __restrict__ db, long rows, int D, long chunk,
+                                                              float* __restrict__ ws) {
   const int c = blockIdx.x * LN_THREADS + threadIdx.x;
   if (c >= D) return;
   const long r0 = (long)blockIdx.y * chunk, r1 = r0 + chunk < rows ? r0 + chunk : rows;
@@ -100,8 +101,36 @@ __global__ void __launch_bounds__(LN_THREADS) ln_param_kernel(const float* __res
     a += d * (x[r * D + c] - mean[r]) * rstd[r];
     bsum += d;
   }
+  if (ws) {                     // deterministic mode: this chunk's partials, summed in chunk order by ln_param_finish
+    ws[((long)blockIdx.y * 2) * D + c] = a;
+    ws[((long)blockIdx.y * 2 + 1) * D + c] = bsum;
+    return;
+  }
   if (dg) atomicAdd(dg + c, a);
   if (db) atomicAdd(db + c, bsum);
+}
+
+// Deterministic mode: dg[c] += sum over chunks (ascending) of ws[chunk][0][c], db[c] likewise from ws[chunk][1][c].
+__global__ void __launch_bounds__(LN_THREADS) ln_param_finish_kernel(const float* __restrict__ ws,
+                                                                     float* __restrict__ dg, float* __restrict__ db,
+                                                                     int D, long chunks) {
+  const int c = blockIdx.x * LN_THREADS + threadIdx.x;
+  if (c >= D) return;
+  float a = 0.f, bsum = 0.f;
+  for (long y = 0; y < chunks; ++y) {
+    a += ws[(y * 2) * D + c];
+    bsum += ws[(y * 2 + 1) * D + c];
+  }
+  if (dg) dg[c] += a;
+  if (db) db[c] += bsum;
+}
+
+// Row chunks of the parameter-gradient pass: 64-row chunks, at most ~2048 blocks. A function of (rows, D) only.
+long param_chunks(long rows, int D) {
+  const int bx = (D + LN_THREADS - 1) / LN_THREADS;
+  long by = (rows + 63) / 64;
+  if ((long)bx * by > 2048) by = (2048 + bx - 1) / bx;
+  return by;
 }
 
 }  // namespace
@@ -115,16 +144,20 @@ int bigdl_layernorm_fwd(const float* x, const float* g, const float* b, float* y
 }
 
 int bigdl_layernorm_bwd(const float* dy, const float* x, const float* g, const float* mean, const float* rstd,
-                        float* dx, float* dg, float* db, long rows, int D, hipStream_t st) {
+                        float* dx, float* dg, float* db, long rows, int D, float* det_ws, hipStream_t st) {
   if (D > LN_THREADS * LN_MAXV || D <= 0 || rows <= 0 || rows > 2147483647L) return -1;
   if (dx) ln_bwd_kernel<<<(unsigned)rows, LN_THREADS, 0, st>>>(dy, x, g, mean, rstd, dx, D);
   if (dg || db) {
     const int bx = (D + LN_THREADS - 1) / LN_THREADS;
-    long by = (rows + 63) / 64;                  // 64-row chunks, at most ~2048 blocks
-    if ((long)bx * by > 2048) by = (2048 + bx - 1) / bx;
+    const long by = param_chunks(rows, D);
     const long chunk = (rows + by - 1) / by;
-    ln_param_kernel<<<dim3(bx, (unsigned)by), LN_THREADS, 0, st>>>(dy, x, mean, rstd, dg, db, rows, D, chunk);
+    float* ws = bigdl_deterministic() ? det_ws : nullptr;
+    if (bigdl_deterministic() && !ws) return -2;
+    ln_param_kernel<<<dim3(bx, (unsigned)by), LN_THREADS, 0, st>>>(dy, x, mean, rstd, dg, db, rows, D, chunk, ws);
+    if (ws) ln_param_finish_kernel<<<bx, LN_THREADS, 0, st>>>(ws, dg, db, D, by);
   }
   HIP_LAUNCH_CHECK();
   return 0;
 }
+
+long bigdl_layernorm_param_chunks(long rows, int D) { return D > 0 && rows > 0 ? param_chunks(rows, D) : 0; }

@@ -204,6 +204,34 @@ __global__ void embedding_bwd_ids_kernel(const void* __restrict__ gout, const ID
   }
 }
 
+// Deterministic mode: the token positions arrive stably sorted by weight row (keys ascending, positions ascending
+// inside a run). One wave per (sorted slot, 64-column slice); the wave whose slot opens a run of a valid key walks the
+// run in order, s = g[first]; s += g[next]; ..., lanes across the columns (coalesced), and adds scale * s to gW once.
+template <bool GB>
+__global__ void embedding_bwd_sorted_kernel(const void* __restrict__ gout, const long* __restrict__ keys,
+                                            const long* __restrict__ pos, float* __restrict__ gW, long rows, int D,
+                                            long nIndex, float scale) {
+  const int lane = threadIdx.x & 63;
+  const long wid = (blockIdx.x * (long)blockDim.x + threadIdx.x) >> 6;
+  const long nw = ((long)gridDim.x * blockDim.x) >> 6;
+  const long slices = (D + 63) / 64;
+  for (long w = wid; w < rows * slices; w += nw) {
+    const long i = w / slices;
+    const int d = (int)(w % slices) * 64 + lane;
+    const long k = keys[i];
+    if (k < 0 || k >= nIndex || (i > 0 && keys[i - 1] == k) || d >= D) continue;
+    float s = 0.f;
+    for (long j = i; j < rows && keys[j] == k; ++j) {
+      const long r = pos[j];
+      float g;
+      if (GB) g = __uint_as_float((unsigned)(static_cast<const bf16_t*>(gout)[r * D + d]) << 16);
+      else g = static_cast<const float*>(gout)[r * D + d];
+      s = j == i ? g : s + g;
+    }
+    gW[k * D + d] += scale * s;
+  }
+}
+
 // ------------------------------------------------------------------------------------------ bilinear resize (NCHW)
 // TF legacy mapping src = dst * scale, scale = in/out (align_corners: (in-1)/(out-1)), clamped at the edge.
 __device__ __forceinline__ void bil_src(int o, int in, float scale, int& i0, int& i1, float& f) {
@@ -358,6 +386,14 @@ void bigdl_embedding_bwd_ids(const void* gout, int gout_bf16, const void* ids, i
 void bigdl_embedding_bwd(const float* gout, const long* idx, float* gW, long rows, int D, long nIndex, float scale,
                          hipStream_t st) {
   embedding_bwd_kernel<<<blocks_for(rows * 64), 256, 0, st>>>(gout, idx, gW, rows, D, nIndex, scale);
+  HIP_LAUNCH_CHECK();
+}
+void bigdl_embedding_bwd_sorted(const void* gout, int gout_bf16, const long* keys, const long* pos, float* gW, long rows,
+                                int D, long nIndex, float scale, hipStream_t st) {
+  if (rows <= 0 || D <= 0) return;
+  const int g = blocks_for(rows * ((D + 63) / 64) * 64);
+  if (gout_bf16) embedding_bwd_sorted_kernel<true><<<g, 256, 0, st>>>(gout, keys, pos, gW, rows, D, nIndex, scale);
+  else embedding_bwd_sorted_kernel<false><<<g, 256, 0, st>>>(gout, keys, pos, gW, rows, D, nIndex, scale);
   HIP_LAUNCH_CHECK();
 }
 void bigdl_resize_bilinear_fwd(const float* x, float* y, long NC, int H, int W, int OH, int OW, float sh, float sw,
