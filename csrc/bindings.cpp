@@ -179,8 +179,8 @@ OptT conv_nt(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
 // (N, C, 2 OH, 2 OW) bf16 channels_last (dx may be a channel slice: row stride ldo), wt the (C, 3, 3, K) transposed
 // weight; optional consumer-BN reduction as conv_nt's. Returns false without launching anything when the kernel does
 // not take the call (the caller runs the four phase GEMMs).
-bool dgrad_s2(const Tensor& dy, const Tensor& wt, const Tensor& out, const OptT& bn_x, const OptT& bn_z,
-              const OptT& bn_mean, const OptT& bn_aff, const OptT& bn_red, const OptT& bn_zm) {
+bool dgrad_s2_call(const Tensor& dy, const Tensor& wt, const Tensor& out, const OptT& bn_x, const OptT& bn_z,
+                   const OptT& bn_mean, const OptT& bn_aff, const OptT& bn_red, const OptT& bn_zm, bool launch) {
   if (dy.dim() != 4 || out.dim() != 4 || wt.dim() != 4 || !dy.is_contiguous(at::MemoryFormat::ChannelsLast) ||
       !wt.is_contiguous() || wt.size(1) != 3 || wt.size(2) != 3 || wt.size(3) != dy.size(1) ||
       wt.size(0) != out.size(1) || out.size(0) != dy.size(0) || out.stride(1) != 1 ||
@@ -205,8 +205,17 @@ bool dgrad_s2(const Tensor& dy, const Tensor& wt, const Tensor& out, const OptT&
                 "dgrad_s2: bn operands");
   }
   if (!bigdl_dgrad_s2_applies(&a)) return false;
-  TORCH_CHECK(bigdl_dgrad_s2(&a, stream()) == 0, "dgrad_s2: launch failed");
+  if (launch) TORCH_CHECK(bigdl_dgrad_s2(&a, stream()) == 0, "dgrad_s2: launch failed");
   return true;
+}
+bool dgrad_s2(const Tensor& dy, const Tensor& wt, const Tensor& out, const OptT& bn_x, const OptT& bn_z,
+              const OptT& bn_mean, const OptT& bn_aff, const OptT& bn_red, const OptT& bn_zm) {
+  return dgrad_s2_call(dy, wt, out, bn_x, bn_z, bn_mean, bn_aff, bn_red, bn_zm, true);
+}
+// Would dgrad_s2 take this call? The same checks on the same operands; launches nothing.
+bool dgrad_s2_applies(const Tensor& dy, const Tensor& wt, const Tensor& out, const OptT& bn_x, const OptT& bn_z,
+                      const OptT& bn_mean, const OptT& bn_aff, const OptT& bn_red, const OptT& bn_zm) {
+  return dgrad_s2_call(dy, wt, out, bn_x, bn_z, bn_mean, bn_aff, bn_red, bn_zm, false);
 }
 
 // Would conv_nt take an addend subsampled by (sh, sw) for this geometry (conv_nt's geo / taps)? bn as conv_stand_in's.
@@ -330,6 +339,11 @@ std::vector<int64_t> conv_wgrad_plan_info(std::vector<int64_t> geo, bool bias) {
   const bool atomic = c.kernel == WGRAD_GLDS_ATOMIC || c.kernel == WGRAD_G3_ATOMIC;
   return {c.kernel == WGRAD_REG ? 0 : atomic ? 1 : c.splits, c.ws_floats, c.kernel == WGRAD_HALO ? c.splits : 0,
           c.kernel == WGRAD_P8 || c.kernel == WGRAD_P8_DIRECT, c.kernel == WGRAD_REG};
+}
+
+// The kernel conv_wgrad would run on this geometry, by name (bigdl_wgrad_kernel_name)
+std::string conv_wgrad_plan_name(std::vector<int64_t> geo, bool bias) {
+  return bigdl_wgrad_kernel_name(wgrad_choice_of(geo, bias, "conv_wgrad_plan_name").kernel);
 }
 
 void transpose_krsc(const Tensor& w, const Tensor& wt, int64_t K, int64_t RS, int64_t C) {
@@ -1757,7 +1771,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dgrad_s2", &dgrad_s2, py::arg("dy"), py::arg("wt"), py::arg("out"), py::arg("bn_x") = py::none(),
         py::arg("bn_z") = py::none(), py::arg("bn_mean") = py::none(), py::arg("bn_aff") = py::none(),
         py::arg("bn_red") = py::none(), py::arg("bn_zm") = py::none());
+  m.def("dgrad_s2_applies", &dgrad_s2_applies, py::arg("dy"), py::arg("wt"), py::arg("out"),
+        py::arg("bn_x") = py::none(), py::arg("bn_z") = py::none(), py::arg("bn_mean") = py::none(),
+        py::arg("bn_aff") = py::none(), py::arg("bn_red") = py::none(), py::arg("bn_zm") = py::none());
   m.def("set_dgrad_s2", &bigdl_set_dgrad_s2);
+  m.def("get_dgrad_s2", &bigdl_get_dgrad_s2);
   m.def("conv_addend_stride_applies", &conv_addend_stride_applies, py::arg("geo"), py::arg("taps"), py::arg("sh"),
         py::arg("sw"), py::arg("bn") = 0);
   m.def("conv_wgrad", &conv_wgrad, py::arg("dy"), py::arg("src"), py::arg("dw"), py::arg("dbias"), py::arg("geo"),
@@ -1928,6 +1946,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_wgrad_p8", &bigdl_set_wgrad_p8);
   m.def("conv_wgrad_uses_p8", &conv_wgrad_uses_p8);
   m.def("conv_wgrad_plan_info", &conv_wgrad_plan_info);
+  m.def("conv_wgrad_plan_name", &conv_wgrad_plan_name);
+  m.def("get_conv_shortk", &bigdl_get_conv_shortk);
+  m.def("get_conv_p8", &bigdl_get_conv_p8);
+  m.def("get_conv_w8", &bigdl_get_conv_w8);
+  m.def("get_conv_sk", &bigdl_get_conv_sk);
+  m.def("get_conv_s1", &bigdl_get_conv_s1);
+  m.def("get_wgrad_p8", &bigdl_get_wgrad_p8);
+  m.def("get_conv_halo", &bigdl_get_conv_halo);
+  m.def("get_stem_fwd", &bigdl_get_stem_fwd);
+  m.def("get_stem_wgrad", &bigdl_get_stem_wgrad);
+  m.def("get_wgrad_halo", &bigdl_get_wgrad_halo);
   m.def("conv_nt_plan_info", &conv_nt_plan_info, py::arg("geo"), py::arg("taps"), py::arg("flags") = 0,
         py::arg("addend_stride") = std::vector<int64_t>());
   m.def("get_conv_g4", &bigdl_get_conv_g4);

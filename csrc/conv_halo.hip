@@ -800,9 +800,7 @@ void launch_halo_i8(const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
 extern "C" {
 
 void bigdl_set_conv_halo(int v) { g_conv_halo = v; }
-
-// 1 when bigdl_conv_halo takes this forward / data-gradient GEMM (BIGDL_CONV_HALO=0 turns it off; 2 / 3: see below)
-int bigdl_conv_halo_applies(const ConvArgs* a) {
+int bigdl_get_conv_halo() {
   if (g_conv_halo < 0) {
     const char* e = getenv("BIGDL_CONV_HALO");
     // default 1: forwards and data gradients (those with a consumer-BN reduction and no addend take the lean
@@ -810,6 +808,12 @@ int bigdl_conv_halo_applies(const ConvArgs* a) {
     // 2 = forwards only, 3 = all but the 56 x 56 data gradients)
     g_conv_halo = e ? atoi(e) : 1;
   }
+  return g_conv_halo;
+}
+
+// 1 when bigdl_conv_halo takes this forward / data-gradient GEMM (BIGDL_CONV_HALO=0 turns it off; 2 / 3: see below)
+int bigdl_conv_halo_applies(const ConvArgs* a) {
+  (void)bigdl_get_conv_halo();     // reads BIGDL_CONV_HALO once
   if (!g_conv_halo || a->ntaps != 9 || a->mul_h != 1 || a->mul_w != 1 || !a->ident_out || a->out32 || a->pstride ||
       a->Hs != a->OH || a->Ws != a->OW || a->Hs != a->Ws || a->Kdim != 9 * a->Cs || (a->Cs % 32) ||
       (a->ldo % 8) || (a->Ncol % 8) || a->ldw < a->Kdim || (a->ldw % 8))
@@ -858,13 +862,16 @@ int bigdl_conv_halo(const ConvArgs* a, hipStream_t st) {
 // tap_h = (r == 0), tap_w = (s == 0), tap_k = t; optional consumer-BN reduction (sign-mask or affine ReLU mask).
 // BIGDL_DGRAD_S2=0 turns it off (the four phase GEMMs of bigdl_conv_nt run instead).
 void bigdl_set_dgrad_s2(int v) { g_dgrad_s2 = v; }
-
-int bigdl_dgrad_s2_applies(const ConvArgs* a) {
+int bigdl_get_dgrad_s2() {
   if (g_dgrad_s2 < 0) {
     const char* e = getenv("BIGDL_DGRAD_S2");
     g_dgrad_s2 = e ? atoi(e) : 1;
   }
-  if (!g_dgrad_s2 || bigdl_get_conv_impl() != 1 || a->ntaps != 9 || a->Kdim != 9 * a->Cs || a->ldw < a->Kdim ||
+  return g_dgrad_s2;
+}
+
+int bigdl_dgrad_s2_applies(const ConvArgs* a) {
+  if (!bigdl_get_dgrad_s2() || bigdl_get_conv_impl() != 1 || a->ntaps != 9 || a->Kdim != 9 * a->Cs || a->ldw < a->Kdim ||
       (a->ldw % 8) || (a->Cs % 32) || (a->Ncol % 8) || (a->ldo % 8) || a->ldo < a->Ncol || a->Hs != a->Ws ||
       a->OH != 2 * a->Hs || a->OW != 2 * a->Ws || !a->ident_out || a->M != a->Nb * a->OH * a->OW || a->Nb < 1)
     return 0;

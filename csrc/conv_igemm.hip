@@ -3227,6 +3227,12 @@ void bigdl_set_wgrad_p8(int v) { sw().wgrad_p8 = v; }
 void bigdl_set_wgrad_g3(int v) { sw().wgrad_g3 = v; }
 void bigdl_set_wgrad_tr_asm(int v) { sw().wgrad_tr_asm = v; }
 int bigdl_get_conv_g4() { return sw().g4; }
+int bigdl_get_conv_shortk() { return sw().shortk; }
+int bigdl_get_conv_p8() { return sw().p8; }
+int bigdl_get_conv_w8() { return sw().w8; }
+int bigdl_get_conv_sk() { return sw().sk; }
+int bigdl_get_conv_s1() { return sw().s1; }
+int bigdl_get_wgrad_p8() { return sw().wgrad_p8; }
 int bigdl_get_conv_impl() { return sw().impl; }
 int bigdl_get_wgrad_g3() { return sw().wgrad_g3 != 0; }
 int bigdl_get_wgrad_tr_asm() { return sw().wgrad_tr_asm != 0; }
@@ -3249,6 +3255,21 @@ const char* bigdl_conv_kernel_name(int kernel) {
     case CONV_GLDS: return "glds";
     case CONV_GLDS_SLOWK: return "glds_slowk";
     case CONV_REG: return "reg";
+    default: return "refused";
+  }
+}
+
+const char* bigdl_wgrad_kernel_name(int kernel) {
+  switch (kernel) {
+    case WGRAD_STEM: return "stem";
+    case WGRAD_HALO: return "halo";
+    case WGRAD_P8_DIRECT: return "p8_direct";
+    case WGRAD_P8: return "p8";
+    case WGRAD_GLDS_WS: return "glds_ws";
+    case WGRAD_G3_WS: return "g3_ws";
+    case WGRAD_GLDS_ATOMIC: return "glds_atomic";
+    case WGRAD_G3_ATOMIC: return "g3_atomic";
+    case WGRAD_REG: return "reg";
     default: return "refused";
   }
 }

@@ -216,6 +216,19 @@ void bigdl_pair_wgrad_add(const float* dwp, float* gw, int K, int C, int R, int 
 // Kernel choice and pixel split for the weight gradient (a->splits / m_per_split / ws are not read), and its launch;
 // 0 on success, else a negative WgradKernel code.
 WgradChoice bigdl_conv_wgrad_choose(const WgradArgs* a);
+const char* bigdl_wgrad_kernel_name(int kernel);
+// current value of every conv switch that has a setter (tests save and restore them)
+int bigdl_get_conv_shortk();
+int bigdl_get_conv_p8();
+int bigdl_get_conv_w8();
+int bigdl_get_conv_sk();
+int bigdl_get_conv_s1();
+int bigdl_get_wgrad_p8();
+int bigdl_get_conv_halo();
+int bigdl_get_dgrad_s2();
+int bigdl_get_stem_fwd();
+int bigdl_get_stem_wgrad();
+int bigdl_get_wgrad_halo();
 int bigdl_conv_wgrad(const WgradArgs* a, const WgradChoice* c, hipStream_t st);
 void bigdl_transpose_krsc(const uint16_t* w, uint16_t* wt, int K, int RS, int C, hipStream_t st);
 // batched form: desc = device int64 [n][6] {w ptr, wt ptr, K, RS, C, first tile}, tiles of 32 x 32 per (rs)

@@ -106,13 +106,16 @@ extern "C" {
 // output rows a multiple of 4, no addend / consumer-BN epilogue. BIGDL_STEM_FWD=0 turns it off.
 static int g_stem_fwd = -1;
 void bigdl_set_stem_fwd(int v) { g_stem_fwd = v; }
-
-int bigdl_stem_fwd_applies(const ConvArgs* a) {
+int bigdl_get_stem_fwd() {
   if (g_stem_fwd < 0) {
     const char* e = getenv("BIGDL_STEM_FWD");
     g_stem_fwd = e ? atoi(e) : 1;
   }
-  if (!g_stem_fwd || a->Cs != 8 || a->ntaps != SR * 4 || a->mul_h != 2 || a->mul_w != 1 || a->OW != SOW || a->Ws != 115 ||
+  return g_stem_fwd;
+}
+
+int bigdl_stem_fwd_applies(const ConvArgs* a) {
+  if (!bigdl_get_stem_fwd() || a->Cs != 8 || a->ntaps != SR * 4 || a->mul_h != 2 || a->mul_w != 1 || a->OW != SOW || a->Ws != 115 ||
       a->OH % SRB || a->Ncol != 64 || a->ldw != SR * 32 || a->Kdim != SR * 32 || !a->ident_out || a->ldo != 64 ||
       a->out32 || a->addend || a->bnred || a->pstride || a->ws)
     return 0;
@@ -350,6 +353,13 @@ extern "C" {
 
 static int g_stem_wgrad = -1;
 void bigdl_set_stem_wgrad(int v) { g_stem_wgrad = v; }
+int bigdl_get_stem_wgrad() {
+  if (g_stem_wgrad < 0) {
+    const char* e = getenv("BIGDL_STEM_WGRAD");
+    g_stem_wgrad = e ? atoi(e) : 1;
+  }
+  return g_stem_wgrad;
+}
 
 static int stem_wgrad_grid() {
   static int cus = 0;
@@ -365,11 +375,7 @@ static int stem_wgrad_grid() {
 // Workspace floats (> 0) when the pair-view stem kernel takes this weight gradient (ops/conv.py conv2d_pairs_wgrad
 // geometry: 8-element pairs, 7 row x 4 pair taps, row stride 2, 112 output columns, 64 channels), else 0.
 long bigdl_stem_wgrad_plan(const WgradArgs* a) {
-  if (g_stem_wgrad < 0) {
-    const char* e = getenv("BIGDL_STEM_WGRAD");
-    g_stem_wgrad = e ? atoi(e) : 1;
-  }
-  if (!g_stem_wgrad || a->Cs != 8 || a->R != SR || a->S != 4 || a->sh != 2 || a->sw != 1 || a->ph || a->pw ||
+  if (!bigdl_get_stem_wgrad() || a->Cs != 8 || a->R != SR || a->S != 4 || a->sh != 2 || a->sw != 1 || a->ph || a->pw ||
       a->dh != 1 || a->dwl != 1 || a->OW != SOW || a->Ws != 115 || (a->OH % SWRB) || a->Ncol != 64 ||
       a->Kdim != SR * 32 || a->ldy != 64 || a->M != a->Nb * a->OH * a->OW || a->Hs < 2 * a->OH + SR - 2)
     return 0;

@@ -451,15 +451,18 @@ int halo_wgs() {
 extern "C" {
 
 void bigdl_set_wgrad_halo(int v) { g_wgrad_halo = v; }
-
-// Splits (>= 1) when the halo kernel takes this weight gradient (sets a->m_per_split = image-row stages per
-// split), 0 otherwise. BIGDL_WGRAD_HALO=0 turns it off.
-int bigdl_wgrad_halo_plan(WgradArgs* a) {
+int bigdl_get_wgrad_halo() {
   if (g_wgrad_halo < 0) {
     const char* e = getenv("BIGDL_WGRAD_HALO");
     g_wgrad_halo = e ? atoi(e) : 1;
   }
-  if (!g_wgrad_halo) return 0;
+  return g_wgrad_halo;
+}
+
+// Splits (>= 1) when the halo kernel takes this weight gradient (sets a->m_per_split = image-row stages per
+// split), 0 otherwise. BIGDL_WGRAD_HALO=0 turns it off.
+int bigdl_wgrad_halo_plan(WgradArgs* a) {
+  if (!bigdl_get_wgrad_halo()) return 0;
   const int rb = halo_rb(a->Ws);
   if (rb == 0 || a->R != 3 || a->S != 3 || a->sh != 1 || a->sw != 1 || a->ph != 1 || a->pw != 1 || a->dh != 1 ||
       a->dwl != 1 || a->OH != a->Hs || a->OW != a->Ws || (a->Hs % rb) || (a->Cs % 64) || (a->Ncol % 64) ||
