@@ -8,7 +8,11 @@ DetectionOutputFrcnn.scala:48-260, BaseModule.scala:25-85.
 
 Compute mapping: the per-RoI inner loops (RoiAlign sampling, RoiPooling max + argmax scatter, NMS IoU tests)
 run in HIP kernels (csrc/detection.hip) when the feature maps live on the GPU; the surrounding bookkeeping
-(top-k, per-class filtering, concatenation) is vectorised torch on the same device. All boxes are fp32 —
+(top-k, per-class filtering, concatenation) is vectorised torch on the same device. On the GPU engine
+BoxPostProcessor, DetectionOutputFrcnn, DetectionOutputSSD and Pooler make one ``multiclass_nms`` /
+``roi_align_levels`` call per forward (every class of every image, every pyramid level, in one launch) and select
+their outputs from the returned mask; ``ops.detection.set_batched(False)`` (BIGDL_DET_BATCHED=0,
+``bigdl.detection.batched``) and the CPU engine run the per-class / per-level loops. All boxes are fp32 —
 box arithmetic is not a bandwidth problem and bf16 boxes would shift pixel coordinates.
 """
 import math
@@ -236,6 +240,13 @@ class Pooler(AbstractModule):
         first = fmaps[1]
         C, dev = first.shape[1], first.device
         res = self.resolution
+        if D.batched(first.is_cuda):
+            # every image and level in one launch; the level assignment stays the fp64 torch arithmetic of _levels
+            r5 = torch.cat([torch.cat([torch.full((r.shape[0], 1), float(b), device=dev), r.to(dev).float()], 1)
+                            for b, r in enumerate(roi_list)], 0)
+            lv = self._levels(r5[:, 1:]).to(torch.int32)
+            maps = [fmaps[level + 1] for level in range(len(self.scales))]
+            return D.roi_align_levels(maps, r5, lv, self.scales, self.samplingRatio, res)
         outs = []
         for b, rois in enumerate(roi_list):
             rois = rois.to(dev).float()
@@ -362,6 +373,30 @@ def _limit_max_per_image(res, max_per_image):
     return out
 
 
+def _mask_max_per_image(keep, scores, max_per_image):
+    """_limit_max_per_image on the (rows, classes) keep mask of one image: keep scores >= the k-th largest kept."""
+    if max_per_image <= 0:
+        return keep
+    kept = scores[keep]
+    total = int(kept.numel())
+    if total <= max_per_image:
+        return keep
+    return keep & (scores >= torch.sort(kept).values[total - max_per_image])
+
+
+def _mask_order(keep, scores, by_score):
+    """(classes, rows, scores) of the kept entries of one image's mask: classes ascending, then rows ascending (the
+    orderWithBBox order) or, with ``by_score``, descending score with ties in row order (the NMS output order)."""
+    cr = torch.nonzero(keep.t())
+    c, r = cr[:, 0], cr[:, 1]
+    s = scores[r, c]
+    if by_score:
+        o = torch.sort(s, descending=True, stable=True).indices
+        o = o[torch.sort(c[o], stable=True).indices]
+        c, r, s = c[o], r[o], s[o]
+    return c, r, s
+
+
 class BoxPostProcessor(AbstractModule):
     """Mask R-CNN box post-processing (reference BoxHead.scala BoxPostProcessor): softmax, weighted box decode,
     clip, per-class NMS, top-``maxPerImage``. Output Table(labels, Table(per-image boxes), scores)."""
@@ -381,6 +416,8 @@ class BoxPostProcessor(AbstractModule):
         prob = torch.softmax(logits.float(), dim=1)
         boxes = D.decode_with_weight(reg.float(), concat, self.weight)
         D.clip_boxes(boxes, float(info.reshape(-1)[0]), float(info.reshape(-1)[1]))
+        if D.batched(reg.is_cuda) and prob.shape[1] == self.nClasses:
+            return self._select_batched(prob, boxes, counts)
         labels, scores, out_boxes = [], [], Table()
         start = 0
         for i, n in enumerate(counts):
@@ -400,6 +437,25 @@ class BoxPostProcessor(AbstractModule):
             scores += ss
         lab = torch.cat(labels) if labels else torch.zeros(0, device=reg.device)
         sco = torch.cat(scores) if scores else torch.zeros(0, device=reg.device)
+        return Table(lab, out_boxes, sco)
+
+    def _select_batched(self, prob, boxes, counts):
+        """The per-image, per-class loop of updateOutput on one multiclass_nms mask: one launch for all images and
+        classes, a fixed number of host round trips per image."""
+        R, C = prob.shape
+        boxes = boxes.reshape(R, C, 4)
+        keep = D.multiclass_nms(prob, boxes, counts, self.scoreThresh, self.nmsThresh, skip_class=0)
+        labels, scores, out_boxes = [], [], Table()
+        start = 0
+        for i, n in enumerate(counts):
+            sc = prob[start:start + n]
+            c, r, s = _mask_order(_mask_max_per_image(keep[start:start + n], sc, self.maxPerImage), sc, False)
+            out_boxes[i + 1] = boxes[start + r, c]
+            labels.append(c.float())
+            scores.append(s)
+            start += n
+        lab = torch.cat(labels) if labels else torch.zeros(0, device=prob.device)
+        sco = torch.cat(scores) if scores else torch.zeros(0, device=prob.device)
         return Table(lab, out_boxes, sco)
 
     def updateGradInput(self, input, gradOutput):
@@ -641,6 +697,19 @@ class DetectionOutputSSD(AbstractModule):
         locs = loc.reshape(B, nP, nl, 4)
         confs = conf.reshape(B, nP, self.nClasses)
         pboxes, pvars = prior[0, 0].reshape(nP, 4), prior[0, 1].reshape(nP, 4)
+        detect = self._detect_batched if D.batched(loc.is_cuda) else self._detect_loop
+        results, counts = detect(locs, confs, pboxes, pvars)
+        maxd = max(counts) if counts else 0
+        out = torch.zeros(B, 1 + maxd * 6, device=loc.device)
+        if sum(counts) > 0:
+            for b in range(B):
+                out[b, 0] = counts[b]
+                out[b, 1: 1 + counts[b] * 6] = results[b].reshape(-1)
+        return out
+
+    def _detect_loop(self, locs, confs, pboxes, pvars):
+        """Per image and class: decode, nms_fast, then the keepTopK selection. Returns (rows per image, counts)."""
+        B, nl = locs.shape[0], locs.shape[2]
         results, counts = [], []
         for b in range(B):
             decoded = [D.decode_boxes(pboxes, pvars, False, locs[b, :, c], self.varianceEncodedInTarget)
@@ -667,15 +736,35 @@ class DetectionOutputSSD(AbstractModule):
                 dets, num = nd, self.keepTopK
             rows = [torch.cat([torch.full((s.numel(), 1), float(c), device=s.device), s[:, None], bx], 1)
                     for c, s, bx in dets if s.numel()]
-            results.append(torch.cat(rows) if rows else torch.zeros(0, 6, device=loc.device))
+            results.append(torch.cat(rows) if rows else torch.zeros(0, 6, device=locs.device))
             counts.append(num)
-        maxd = max(counts) if counts else 0
-        out = torch.zeros(B, 1 + maxd * 6, device=loc.device)
-        if sum(counts) > 0:
-            for b in range(B):
-                out[b, 0] = counts[b]
-                out[b, 1: 1 + counts[b] * 6] = results[b].reshape(-1)
-        return out
+        return results, counts
+
+    def _detect_batched(self, locs, confs, pboxes, pvars):
+        """What _detect_loop computes, from one multiclass_nms mask: one decode and one NMS launch
+        for all images and classes, then the keepTopK selection per image. Returns (rows per image, counts)."""
+        B, nP, nl = locs.shape[0], locs.shape[1], locs.shape[2]
+
+        def tile(p):
+            return p[None, :, None, :].expand(B, nP, nl, 4).reshape(-1, 4)
+
+        dec = D.decode_boxes(tile(pboxes), tile(pvars), False, locs.reshape(-1, 4),
+                             self.varianceEncodedInTarget).reshape(B * nP, nl, 4)
+        skip = self.bgLabel if 0 <= self.bgLabel < self.nClasses else -1
+        keep = D.multiclass_nms(confs.reshape(B * nP, self.nClasses), dec, [nP] * B, self.confThresh, self.nmsThresh,
+                                skip_class=skip, inclusive=True, pre_topk=self.nmsTopk, normalized=True)
+        results, counts = [], []
+        for b in range(B):
+            c, r, s = _mask_order(keep[b * nP:(b + 1) * nP], confs[b], True)
+            num = int(c.numel())
+            if -1 < self.keepTopK < num:
+                top = torch.zeros(num, dtype=torch.bool, device=s.device)
+                top[torch.sort(s, descending=True, stable=True).indices[: self.keepTopK]] = True
+                c, r, s, num = c[top], r[top], s[top], self.keepTopK
+            bx = dec[b * nP + r, c if nl > 1 else torch.zeros_like(c)]
+            results.append(torch.cat([c.float()[:, None], s[:, None], bx], 1))
+            counts.append(num)
+        return results, counts
 
     def updateGradInput(self, input, gradOutput):
         return gradOutput
@@ -697,6 +786,8 @@ class DetectionOutputFrcnn(AbstractModule):
         pred = D.bbox_transform_inv(boxes, deltas.float())
         D.clip_boxes(pred, float(iv[0] / iv[2]), float(iv[1] / iv[3]))
         res = [None] * self.nClasses
+        if not self.bboxVote and D.batched(scores.is_cuda) and scores.shape[1] == self.nClasses:
+            return self._process_batched(scores, pred)
         for c in range(1, self.nClasses):
             inds = torch.nonzero(scores[:, c] > self.thresh).reshape(-1)
             if inds.numel() == 0:
@@ -709,6 +800,20 @@ class DetectionOutputFrcnn(AbstractModule):
             res[c] = (ks, kb)
         # reference filters on the last box column (a bug); the score threshold is what is meant
         return _limit_max_per_image(res, self.maxPerImage)
+
+    def _process_batched(self, scores, pred):
+        """The per-class loop of process (without bboxVote) on one multiclass_nms mask: all classes in one launch;
+        the mask is cut to maxPerImage and split back into per-class (scores, boxes) in NMS output order."""
+        R = scores.shape[0]
+        pred = pred.reshape(R, self.nClasses, 4)
+        keep = D.multiclass_nms(scores, pred, [R], self.thresh, self.nmsThresh, skip_class=0)
+        c, r, s = _mask_order(_mask_max_per_image(keep, scores, self.maxPerImage), scores, True)
+        res, start = [None] * self.nClasses, 0
+        for k, n in enumerate(torch.bincount(c, minlength=self.nClasses).tolist()):
+            if n:
+                res[k] = (s[start:start + n], pred[r[start:start + n], k])
+            start += n
+        return res
 
     def updateOutput(self, input):
         if self.train:

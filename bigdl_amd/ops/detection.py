@@ -4,10 +4,12 @@ Reference: S/nn/Nms.scala:26-236, S/nn/RoiAlign.scala:45-420, S/nn/RoiPooling.sc
 S/transform/vision/image/util/BboxUtil.scala:26-581.
 
 On a GPU tensor the HIP kernels in csrc/detection.hip run (IoU bitmask NMS with a single-wave greedy scan,
-one-thread-per-output RoiAlign / RoiPooling); on the CPU the same arithmetic runs in numpy / torch. Box
+one-thread-per-output RoiAlign / RoiPooling; ``multiclass_nms`` and ``roi_align_levels`` cover all classes of all
+images, or all pyramid levels, in one launch each); on the CPU the same arithmetic runs in numpy / torch. Box
 conventions follow the reference: pixel boxes use ``+1`` widths (``(x2 - x1 + 1)``) unless ``normalized``.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -99,6 +101,146 @@ def nms_fast(scores, boxes, nms_thresh, score_thresh, topk=-1, eta=1.0, normaliz
             if eta < 1 and thr > 0.5:
                 thr *= eta
     return order[torch.as_tensor(keep, dtype=torch.long, device=order.device)]
+
+
+# ------------------------------------------------------------------------------- batched detection ops
+# multiclass_nms / roi_align_levels run every (image, class) segment, or every pyramid level, in one launch
+# (csrc/detection.hip nms_classes_kernel / roi_align_levels_fwd_kernel): BIGDL_DET_BATCHED / Engine property
+# bigdl.detection.batched / set_batched; unset means on for GPU tensors. Off, or on the CPU, the same results come
+# from the per-class / per-level loops below, which are also what an overflowing call falls back to.
+_BATCHED = [None]
+_ROUTE = {"multiclass_nms": None, "roi_align_levels": None, "last": None}
+NMS_CLASSES_MIN_CAP = 256                      # smallest LDS capacity nms_classes_kernel is instantiated for
+
+
+def set_batched(v):
+    """True / False, "1" / "0", or None for the engine's default."""
+    _BATCHED[0] = None if v is None or v == "" else str(v).lower() in ("1", "true", "yes")
+
+
+def batched(is_cuda):
+    v = _BATCHED[0]
+    if v is None:
+        env = os.environ.get("BIGDL_DET_BATCHED", "")
+        v = True if env == "" else env.lower() in ("1", "true", "yes")
+    return bool(v) and bool(is_cuda)
+
+
+def last_route(op=None):
+    """"batched", "loop" or "overflow": the path the last call of ``op`` ("multiclass_nms" / "roi_align_levels")
+    took; without ``op``, of whichever of the two ran last."""
+    return _ROUTE["last" if op is None else op]
+
+
+def _set_route(op, route):
+    _ROUTE[op] = _ROUTE["last"] = route
+
+
+def _offsets(counts):
+    off = [0]
+    for n in counts:
+        off.append(off[-1] + int(n))
+    return off
+
+
+def _multiclass_nms_loop(scores, boxes, off, score_thresh, nms_thresh, skip_class, inclusive, pre_topk, normalized):
+    R, C = scores.shape
+    Cb = boxes.shape[1]
+    keep = torch.zeros(R, C, dtype=torch.bool, device=scores.device)
+    for b in range(len(off) - 1):
+        lo, hi = off[b], off[b + 1]
+        if hi == lo:
+            continue
+        for c in range(C):
+            if c == skip_class:
+                continue
+            s, bx = scores[lo:hi, c], boxes[lo:hi, c if Cb > 1 else 0]
+            if inclusive:
+                kept = nms_fast(s, bx, nms_thresh, score_thresh, pre_topk, 1.0, normalized)
+            else:
+                cand = torch.nonzero(s > score_thresh).reshape(-1)
+                if cand.numel() == 0:
+                    continue
+                order = cand[torch.sort(s[cand], descending=True, stable=True).indices]
+                if pre_topk > 0:
+                    order = order[:pre_topk]
+                kept = order[nms_sorted(bx[order], nms_thresh, normalized)]
+            keep[lo + kept, c] = True
+    return keep
+
+
+def nms_classes_launch(scores, boxes, off, score_thresh, nms_thresh, skip_class, inclusive, pre_topk, normalized,
+                       keep, overflow, cap=0):
+    """The launch of nms_classes_kernel alone (no read-back, graph-capturable): keep uint8 [R, C] is rewritten in
+    full, overflow int32 [1] is set when a segment holds more candidates than the capacity. Returns the capacity."""
+    # nms_fast takes every row when its threshold is not positive
+    thr = float("-inf") if inclusive and score_thresh <= 0 else float(score_thresh)
+    return native.get().nms_classes(scores, boxes, [int(o) for o in off], int(skip_class), thr, bool(inclusive),
+                                    int(pre_topk), float(nms_thresh), bool(normalized), keep, overflow, int(cap))
+
+
+def multiclass_nms(scores, boxes, counts, score_thresh, nms_thresh, skip_class=0, inclusive=False, pre_topk=-1,
+                   normalized=False, cap=0):
+    """Greedy NMS of every (image, class) segment. scores (R, C); boxes (R, Cb, 4) or (R, Cb * 4) with Cb == C or
+    Cb == 1 (class-shared boxes); counts = rows per image. A row is a candidate of its class when
+    ``score > score_thresh`` (``>=`` with ``inclusive``, the SSD rule); candidates are taken in descending score
+    order (ties: lower row first), cut to ``pre_topk`` when positive, and suppressed greedily at ``nms_thresh``.
+    Returns the bool (R, C) mask of kept rows; column ``skip_class`` stays False.
+
+    On the GPU with batching on this is one launch plus the read of the overflow word (the one synchronisation);
+    an overflowing call, the CPU, and batching off run the per-class loop, which computes the same mask. ``cap``
+    forces the kernel's candidate capacity per segment (256, 1024 or 4096; 0 = from the longest image)."""
+    R, C = scores.shape
+    boxes = boxes.reshape(R, -1, 4)
+    off = _offsets(counts)
+    assert off[-1] == R, "multiclass_nms: counts must sum to the number of rows"
+    assert boxes.shape[1] in (1, C), "multiclass_nms: boxes must be per class or shared"
+    route = "loop"
+    if batched(_on_gpu(scores)) and R:
+        s, bx = scores.float().contiguous(), boxes.float().contiguous()
+        keep = torch.empty(R, C, dtype=torch.uint8, device=s.device)
+        overflow = torch.empty(1, dtype=torch.int32, device=s.device)
+        nms_classes_launch(s, bx, off, score_thresh, nms_thresh, skip_class, inclusive, pre_topk, normalized, keep,
+                           overflow, cap)
+        if int(overflow.item()) == 0:
+            _set_route("multiclass_nms", "batched")
+            return keep.bool()
+        route = "overflow"
+    keep = _multiclass_nms_loop(scores, boxes, off, score_thresh, nms_thresh, skip_class, inclusive, pre_topk,
+                                normalized)
+    _set_route("multiclass_nms", route)
+    return keep
+
+
+def _roi_align_levels_loop(fmaps, rois5, levels, scales, sampling_ratio, res):
+    C = fmaps[0].shape[1]
+    out = torch.zeros(rois5.shape[0], C, res, res, dtype=torch.float32, device=fmaps[0].device)
+    lv = levels.clamp(0, len(fmaps) - 1)
+    for level in range(len(fmaps)):
+        idx = torch.nonzero(lv == level).reshape(-1)
+        if idx.numel() == 0:
+            continue
+        out[idx] = roi_align(fmaps[level], rois5[idx], scales[level], sampling_ratio, res, res)
+    return out
+
+
+def roi_align_levels(fmaps, rois5, levels, scales, sampling_ratio, res):
+    """RoiAlign of rois5 (R, 5: batch index, x1, y1, x2, y2) where roi r samples ``fmaps[levels[r]]`` (N, C, H_l,
+    W_l) at ``scales[levels[r]]``; levels outside [0, L-1] are clamped. One launch on the GPU with batching on
+    (up to 8 levels), the per-level ``roi_align`` loop otherwise; the two are bit-equal. Returns (R, C, res, res)."""
+    fmaps = list(fmaps)
+    first = fmaps[0]
+    R = rois5.shape[0]
+    if batched(_on_gpu(first)) and len(fmaps) <= 8:
+        out = torch.empty(R, first.shape[1], res, res, dtype=torch.float32, device=first.device)
+        if R:
+            native.get().roi_align_levels_fwd([f.float().contiguous() for f in fmaps], rois5.float().contiguous(),
+                                              levels.to(torch.int32).contiguous(), out,
+                                              [float(s) for s in scales], int(sampling_ratio))
+        _set_route("roi_align_levels", "batched")
+        return out
+    _set_route("roi_align_levels", "loop")
+    return _roi_align_levels_loop(fmaps, rois5, levels, scales, sampling_ratio, res)
 
 
 # ------------------------------------------------------------------------------------------- RoiAlign

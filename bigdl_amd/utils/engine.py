@@ -171,6 +171,10 @@ class _Engine:
             from ..ops import attention
 
             attention.set_decode_native(v)
+        elif k == "bigdl.detection.batched":        # per-class NMS / per-level RoiAlign as one launch each
+            from ..ops import detection
+
+            detection.set_batched(v)
         elif k == "bigdl.module.deviceTiming":      # getTimes in device time (HIP events) for GPU modules
             from ..nn import abstractnn
 

@@ -1077,6 +1077,66 @@ void roi_align_fwd(const Tensor& x, const Tensor& rois, const Tensor& out, doubl
                       (int)out.size(3), (float)scale, (int)sampling, stream());
 }
 
+// scores [R, C], boxes [R, Cb, 4] (Cb == C or 1), offsets = B + 1 host row offsets; keep uint8 [R, C] is written in
+// full, overflow int32 [1]. cap 0 lets the launcher choose the LDS capacity; returns the capacity used.
+int64_t nms_classes(const Tensor& scores, const Tensor& boxes, std::vector<int64_t> offsets, int64_t skip_class,
+                    double score_thresh, bool inclusive, int64_t pre_topk, double nms_thresh, bool normalized,
+                    const Tensor& keep, const Tensor& overflow, int64_t cap) {
+  check_f32(scores, "nms_classes scores"); check_f32(boxes, "nms_classes boxes");
+  TORCH_CHECK(scores.dim() == 2 && boxes.dim() == 3 && boxes.size(2) == 4 && boxes.size(0) == scores.size(0),
+              "nms_classes: scores [R, C], boxes [R, Cb, 4]");
+  const int64_t R = scores.size(0), C = scores.size(1), Cb = boxes.size(1);
+  TORCH_CHECK(C >= 1 && (Cb == 1 || Cb == C), "nms_classes: Cb must be 1 or C");
+  TORCH_CHECK(R * C < (int64_t(1) << 31), "nms_classes: R * C must fit 31 bits");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(boxes.data_ptr()) % 16 == 0, "nms_classes: boxes must be 16-byte aligned");
+  TORCH_CHECK(keep.is_cuda() && keep.is_contiguous() && keep.scalar_type() == at::kByte && keep.dim() == 2 &&
+                  keep.size(0) == R && keep.size(1) == C, "nms_classes: keep must be a contiguous uint8 [R, C]");
+  TORCH_CHECK(overflow.is_cuda() && overflow.scalar_type() == at::kInt && overflow.numel() >= 1,
+              "nms_classes: overflow int32 [1]");
+  TORCH_CHECK(offsets.size() >= 1 && offsets.front() == 0 && offsets.back() == R,
+              "nms_classes: offsets must start at 0 and end at R");
+  std::vector<int> off(offsets.size());
+  for (size_t i = 0; i < offsets.size(); ++i) {
+    TORCH_CHECK(i == 0 || offsets[i] >= offsets[i - 1], "nms_classes: offsets must be monotone");
+    off[i] = (int)offsets[i];
+  }
+  TORCH_CHECK(cap == 0 || cap == 256 || cap == 1024 || cap == 4096, "nms_classes: cap must be 0, 256, 1024 or 4096");
+  const int rc = bigdl_nms_classes(scores.data_ptr<float>(), boxes.data_ptr<float>(), keep.data_ptr<uint8_t>(),
+                                   overflow.data_ptr<int>(), off.data(), (int)off.size() - 1, (int)C, (int)Cb,
+                                   (int)skip_class, (float)score_thresh, inclusive ? 1 : 0, (int)pre_topk,
+                                   (float)nms_thresh, normalized ? 1 : 0, (int)cap, stream());
+  TORCH_CHECK(rc >= 0, "nms_classes failed");
+  return rc;
+}
+
+// fmaps: L <= 8 maps [N, C, H_l, W_l]; rois [R, 5] with the batch index first; levels int32 [R]; out [R, C, PH, PW]
+void roi_align_levels_fwd(std::vector<Tensor> fmaps, const Tensor& rois, const Tensor& levels, const Tensor& out,
+                          std::vector<double> scales, int64_t sampling) {
+  check_f32(rois, "roi_align_levels rois"); check_f32(out, "roi_align_levels out");
+  const int64_t L = (int64_t)fmaps.size();
+  TORCH_CHECK(L >= 1 && L <= BIGDL_ROI_MAX_LEVELS && (int64_t)scales.size() == L,
+              "roi_align_levels: 1 to 8 maps, one scale each");
+  TORCH_CHECK(rois.dim() == 2 && rois.size(1) == 5 && out.dim() == 4 && out.size(0) == rois.size(0),
+              "roi_align_levels: rois [R, 5], out [R, C, PH, PW]");
+  TORCH_CHECK(levels.is_cuda() && levels.is_contiguous() && levels.scalar_type() == at::kInt &&
+                  levels.numel() == rois.size(0), "roi_align_levels: levels must be a contiguous int32 [R]");
+  RoiLevelMaps maps{};
+  maps.L = (int)L; maps.N = (int)fmaps[0].size(0); maps.C = (int)fmaps[0].size(1);
+  for (int64_t l = 0; l < L; ++l) {
+    const Tensor& x = fmaps[l];
+    check_f32(x, "roi_align_levels map");
+    TORCH_CHECK(x.dim() == 4 && x.size(0) == maps.N && x.size(1) == maps.C && x.size(2) >= 1 && x.size(3) >= 1,
+                "roi_align_levels: every map must be [N, C, H, W] with the same N and C");
+    maps.x[l] = x.data_ptr<float>(); maps.H[l] = (int)x.size(2); maps.W[l] = (int)x.size(3);
+    maps.scale[l] = (float)scales[l];
+  }
+  TORCH_CHECK(maps.N >= 1 && out.size(1) == maps.C, "roi_align_levels: shapes");
+  const int rc = bigdl_roi_align_levels_fwd(&maps, rois.data_ptr<float>(), levels.data_ptr<int>(),
+                                            out.data_ptr<float>(), (int)rois.size(0), (int)out.size(2),
+                                            (int)out.size(3), (int)sampling, stream());
+  TORCH_CHECK(rc == 0, "roi_align_levels failed");
+}
+
 void roi_pool_fwd(const Tensor& x, const Tensor& rois, const Tensor& out, const Tensor& argmax, double scale) {
   check_f32(x, "roi_pool x"); check_f32(rois, "roi_pool rois"); check_f32(out, "roi_pool out");
   TORCH_CHECK(x.dim() == 4 && rois.dim() == 2 && rois.size(1) == 5 && out.dim() == 4 && out.size(0) == rois.size(0) &&
@@ -1863,6 +1923,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequantize_rows", &dequantize_rows);
   m.def("nms", &nms);
   m.def("roi_align_fwd", &roi_align_fwd);
+  m.def("nms_classes", &nms_classes, py::arg("scores"), py::arg("boxes"), py::arg("offsets"), py::arg("skip_class"),
+        py::arg("score_thresh"), py::arg("inclusive"), py::arg("pre_topk"), py::arg("nms_thresh"),
+        py::arg("normalized"), py::arg("keep"), py::arg("overflow"), py::arg("cap") = 0);
+  m.def("roi_align_levels_fwd", &roi_align_levels_fwd);
   m.def("roi_pool_fwd", &roi_pool_fwd);
   m.def("roi_pool_bwd", &roi_pool_bwd);
   m.def("lrn_fwd", &lrn_fwd);

@@ -1,5 +1,7 @@
-// Detection kernels for gfx950: greedy NMS (64-bit IoU masks + single-wave scan), RoiAlign forward,
-// RoiPooling forward/backward.
+// Detection kernels for gfx950: greedy NMS (64-bit IoU masks + single-wave scan), segmented NMS over every
+// (image, class) column of a score matrix in one launch (nms_classes_kernel: threshold, sort, top-k cut and greedy
+// pass in LDS, one workgroup per segment), RoiAlign forward for one map or for all pyramid levels in one launch
+// (roi_align_levels_fwd_kernel; both call roi_align_bin), RoiPooling forward/backward.
 //
 // Reference semantics: S/nn/Nms.scala:50-236 (greedy NMS over score-sorted boxes, "IoU > thresh" suppresses,
 // pixel areas (x2-x1+1)(y2-y1+1) unless normalized), S/nn/RoiAlign.scala:45-420 (bilinear sampling grid,
@@ -86,7 +88,134 @@ __global__ void __launch_bounds__(64) nms_scan_kernel(const unsigned long long* 
   if (lane == 0) count_out[0] = kept;
 }
 
+// ------------------------------------------------------------------------------- segmented (image, class) NMS
+// One 256-thread workgroup per (image, class) column slice of scores [R][C]: the rows of image b that pass the
+// score test are compacted into LDS in row order (ballot + popcount per wave, wave counts through LDS), sorted by
+// (score descending, row ascending) with a bitonic network (the composite compare makes the order total, which is
+// the order of a stable descending sort), cut to pre_topk, and walked greedily: when candidate i is alive every
+// thread tests its own candidates j > i with iou_gt and clears their alive bytes; a removed candidate is skipped by
+// all threads, which read the same byte, so there is one barrier per kept box. Areas sit in LDS for j and in
+// registers for i exactly as in nms_mask_kernel, so both kernels evaluate the same expression. No global
+// workspace, no atomics, every loop bounded by the candidate count.
+constexpr int NMS_MAX_IMAGES = 64;   // row offsets travel by value; the launcher issues one launch per 64 images
+struct NmsOffsets { int off[NMS_MAX_IMAGES + 1]; };
+
+template <int CAP>
+__global__ void __launch_bounds__(256) nms_classes_kernel(const float* __restrict__ scores,
+                                                          const float* __restrict__ boxes,
+                                                          unsigned char* __restrict__ keep, int* __restrict__ overflow,
+                                                          NmsOffsets offs, int C, int Cb, int skip_class,
+                                                          float score_thresh, int inclusive, int pre_topk,
+                                                          float nms_thresh, int normalized) {
+  __shared__ float key_s[CAP];
+  __shared__ int key_r[CAP];
+  __shared__ float box[CAP][4];
+  __shared__ float box_area[CAP];
+  __shared__ unsigned char alive[CAP];
+  __shared__ int wave_cnt[4];
+  const int b = blockIdx.x / C, c = blockIdx.x % C, tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int row0 = offs.off[b], nrows = offs.off[b + 1] - row0;
+  for (int r = tid; r < nrows; r += 256) keep[(size_t)(row0 + r) * C + c] = 0;
+  if (c == skip_class) return;
+
+  int n = 0;                                            // candidates so far (workgroup-uniform)
+  for (int base = 0; base < nrows; base += 256) {
+    const int r = base + tid;
+    float s = 0.f;
+    bool p = false;
+    if (r < nrows) {
+      s = scores[(size_t)(row0 + r) * C + c];
+      p = inclusive ? s >= score_thresh : s > score_thresh;   // NaN fails both
+    }
+    const unsigned long long m = __ballot(p);
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int pos = n + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) pos += wave_cnt[w];
+    if (p && pos < CAP) { key_s[pos] = s; key_r[pos] = r; }
+    n += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    __syncthreads();
+  }
+  if (n > CAP) {                                        // the caller reruns this call on the per-class path
+    if (tid == 0) overflow[0] = 1;
+    return;
+  }
+  if (n == 0) return;
+
+  int P = 2;
+  while (P < n) P <<= 1;                                // n <= CAP and CAP is a power of two
+  for (int t = n + tid; t < P; t += 256) { key_s[t] = -INFINITY; key_r[t] = 0x7fffffff; }
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < P / 2; t += 256) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool up = (lo & size) == 0;
+        const float sa = key_s[lo], sb = key_s[hi];
+        const int ra = key_r[lo], rb = key_r[hi];
+        const bool after = sa < sb || (sa == sb && ra > rb);   // a belongs behind b
+        if (after == up) {
+          key_s[lo] = sb; key_s[hi] = sa;
+          key_r[lo] = rb; key_r[hi] = ra;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (pre_topk > 0 && n > pre_topk) n = pre_topk;
+
+  const float one = normalized ? 0.f : 1.f;
+  const int cb = Cb == 1 ? 0 : c;
+  for (int t = tid; t < n; t += 256) {
+    const float4 v = *reinterpret_cast<const float4*>(boxes + ((size_t)(row0 + key_r[t]) * Cb + cb) * 4);
+    box[t][0] = v.x; box[t][1] = v.y; box[t][2] = v.z; box[t][3] = v.w;
+    box_area[t] = (v.z - v.x + one) * (v.w - v.y + one);
+    alive[t] = 1;
+  }
+  __syncthreads();
+  for (int i = 0; i < n; ++i) {
+    if (!alive[i]) continue;                            // same byte for every thread: uniform
+    const float a[4] = {box[i][0], box[i][1], box[i][2], box[i][3]};
+    const float area_i = (a[2] - a[0] + one) * (a[3] - a[1] + one);
+    int j = (i + 1) - ((i + 1) & 255) + tid;            // first j > i owned by this thread
+    if (j <= i) j += 256;
+    for (; j < n; j += 256)
+      if (alive[j] && iou_gt(a, box[j], area_i, box_area[j], nms_thresh, one)) alive[j] = 0;
+    __syncthreads();
+  }
+  for (int t = tid; t < n; t += 256)
+    if (alive[t]) keep[(size_t)(row0 + key_r[t]) * C + c] = 1;
+}
+
 // ---------------------------------------------------------------------------------------------- RoiAlign
+// One output bin (ph, pw) of one roi on one channel plane xc [H][W]; rb = (x1, y1, x2, y2).
+__device__ __forceinline__ float roi_align_bin(const float* __restrict__ xc, const float* __restrict__ rb, int H,
+                                               int W, int PH, int PW, int ph, int pw, float scale, int sampling) {
+  const float sw = rb[0] * scale, sh = rb[1] * scale, ew = rb[2] * scale, eh = rb[3] * scale;
+  const float rw = fmaxf(ew - sw, 1.f), rh = fmaxf(eh - sh, 1.f);
+  const float bh = rh / PH, bw = rw / PW;
+  const int gh = sampling > 0 ? sampling : (int)ceilf(rh / PH);
+  const int gw = sampling > 0 ? sampling : (int)ceilf(rw / PW);
+  float acc = 0.f;
+  for (int iy = 0; iy < gh; ++iy) {
+    const float yy = sh + ph * bh + (iy + 0.5f) * bh / gh;
+    for (int ix = 0; ix < gw; ++ix) {
+      const float xx = sw + pw * bw + (ix + 0.5f) * bw / gw;
+      if (yy < -1.f || yy > (float)H || xx < -1.f || xx > (float)W) continue;
+      float y = fmaxf(yy, 0.f), xv = fmaxf(xx, 0.f);
+      int yl = (int)y, xl = (int)xv, yh, xh;
+      if (yl >= H - 1) { yl = yh = H - 1; y = (float)yl; } else { yh = yl + 1; }
+      if (xl >= W - 1) { xl = xh = W - 1; xv = (float)xl; } else { xh = xl + 1; }
+      const float ly = y - yl, lx = xv - xl, hy = 1.f - ly, hx = 1.f - lx;
+      acc += hy * hx * xc[yl * W + xl] + hy * lx * xc[yl * W + xh] + ly * hx * xc[yh * W + xl] +
+             ly * lx * xc[yh * W + xh];
+    }
+  }
+  return acc / (float)(gh * gw);
+}
+
 // x: [N][C][H][W] fp32; rois: [R][rcols] (rcols 4: batch 0, (x1,y1,x2,y2); rcols 5: (b, x1, y1, x2, y2)).
 // One thread per output element (r, c, ph, pw): the sampling grid of one bin is at most a few dozen taps.
 __global__ void __launch_bounds__(256) roi_align_fwd_kernel(const float* __restrict__ x, const float* __restrict__ rois,
@@ -101,28 +230,30 @@ __global__ void __launch_bounds__(256) roi_align_fwd_kernel(const float* __restr
     const float* roi = rois + (size_t)r * rcols;
     const int b = rcols == 5 ? (int)roi[0] : 0;
     const float* rb = roi + (rcols == 5 ? 1 : 0);
-    const float sw = rb[0] * scale, sh = rb[1] * scale, ew = rb[2] * scale, eh = rb[3] * scale;
-    const float rw = fmaxf(ew - sw, 1.f), rh = fmaxf(eh - sh, 1.f);
-    const float bh = rh / PH, bw = rw / PW;
-    const int gh = sampling > 0 ? sampling : (int)ceilf(rh / PH);
-    const int gw = sampling > 0 ? sampling : (int)ceilf(rw / PW);
     const float* xc = x + ((size_t)b * C + c) * (size_t)H * W;
-    float acc = 0.f;
-    for (int iy = 0; iy < gh; ++iy) {
-      const float yy = sh + ph * bh + (iy + 0.5f) * bh / gh;
-      for (int ix = 0; ix < gw; ++ix) {
-        const float xx = sw + pw * bw + (ix + 0.5f) * bw / gw;
-        if (yy < -1.f || yy > (float)H || xx < -1.f || xx > (float)W) continue;
-        float y = fmaxf(yy, 0.f), xv = fmaxf(xx, 0.f);
-        int yl = (int)y, xl = (int)xv, yh, xh;
-        if (yl >= H - 1) { yl = yh = H - 1; y = (float)yl; } else { yh = yl + 1; }
-        if (xl >= W - 1) { xl = xh = W - 1; xv = (float)xl; } else { xh = xl + 1; }
-        const float ly = y - yl, lx = xv - xl, hy = 1.f - ly, hx = 1.f - lx;
-        acc += hy * hx * xc[yl * W + xl] + hy * lx * xc[yl * W + xh] + ly * hx * xc[yh * W + xl] +
-               ly * lx * xc[yh * W + xh];
-      }
-    }
-    out[idx] = acc / (float)(gh * gw);
+    out[idx] = roi_align_bin(xc, rb, H, W, PH, PW, ph, pw, scale, sampling);
+  }
+}
+
+// All pyramid levels in one launch: roi r samples the map of levels[r]. The level and the batch index are clamped to
+// the maps that exist, so a bad index tensor cannot read out of bounds.
+__global__ void __launch_bounds__(256) roi_align_levels_fwd_kernel(RoiLevelMaps maps, const float* __restrict__ rois,
+                                                                   const int* __restrict__ levels,
+                                                                   float* __restrict__ out, int R, int PH, int PW,
+                                                                   int sampling) {
+  const int C = maps.C;
+  const long total = (long)R * C * PH * PW;
+  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int pw = (int)(idx % PW);
+    const int ph = (int)((idx / PW) % PH);
+    const int c = (int)((idx / ((long)PW * PH)) % C);
+    const int r = (int)(idx / ((long)PW * PH * C));
+    const float* roi = rois + (size_t)r * 5;
+    const int l = min(max(levels[r], 0), maps.L - 1);
+    const int b = min(max((int)roi[0], 0), maps.N - 1);
+    const int H = maps.H[l], W = maps.W[l];
+    const float* xc = maps.x[l] + ((size_t)b * C + c) * (size_t)H * W;
+    out[idx] = roi_align_bin(xc, roi + 1, H, W, PH, PW, ph, pw, maps.scale[l], sampling);
   }
 }
 
@@ -194,6 +325,45 @@ int bigdl_roi_align_fwd(const float* x, const float* rois, float* out, int R, in
   const long total = (long)R * C * PH * PW;
   if (total <= 0) return 0;
   roi_align_fwd_kernel<<<grid_for(total), 256, 0, st>>>(x, rois, out, R, rcols, C, H, W, PH, PW, scale, sampling);
+  HIP_LAUNCH_CHECK();
+  return 0;
+}
+
+int bigdl_nms_classes(const float* scores, const float* boxes, unsigned char* keep, int* overflow,
+                      const int* offsets_host, int B, int C, int Cb, int skip_class, float score_thresh,
+                      int inclusive, int pre_topk, float nms_thresh, int normalized, int cap, hipStream_t st) {
+  if (B < 0 || C <= 0 || (Cb != 1 && Cb != C)) return -1;
+  int longest = 0;
+  for (int b = 0; b < B; ++b) {
+    if (offsets_host[b + 1] < offsets_host[b]) return -1;
+    longest = std::max(longest, offsets_host[b + 1] - offsets_host[b]);
+  }
+  if (cap == 0) cap = longest <= 256 ? 256 : longest <= 1024 ? 1024 : 4096;
+  if (cap != 256 && cap != 1024 && cap != 4096) return -1;
+  bigdl_fill_bytes(overflow, 0, (long)sizeof(int), st);
+  for (int b0 = 0; b0 < B; b0 += NMS_MAX_IMAGES) {
+    const int nb = std::min(NMS_MAX_IMAGES, B - b0);
+    if (offsets_host[b0 + nb] == offsets_host[b0]) continue;
+    NmsOffsets offs{};
+    for (int b = 0; b <= nb; ++b) offs.off[b] = offsets_host[b0 + b];
+#define BIGDL_NMS_CLASSES_LAUNCH(CAP)                                                                             \
+  nms_classes_kernel<CAP><<<nb * C, 256, 0, st>>>(scores, boxes, keep, overflow, offs, C, Cb, skip_class,        \
+                                                  score_thresh, inclusive, pre_topk, nms_thresh, normalized)
+    if (cap == 256) BIGDL_NMS_CLASSES_LAUNCH(256);
+    else if (cap == 1024) BIGDL_NMS_CLASSES_LAUNCH(1024);
+    else BIGDL_NMS_CLASSES_LAUNCH(4096);
+#undef BIGDL_NMS_CLASSES_LAUNCH
+    HIP_LAUNCH_CHECK();
+  }
+  return cap;
+}
+
+int bigdl_roi_align_levels_fwd(const RoiLevelMaps* maps, const float* rois, const int* levels, float* out, int R,
+                               int PH, int PW, int sampling, hipStream_t st) {
+  if (maps->L < 1 || maps->L > BIGDL_ROI_MAX_LEVELS || maps->N < 1) return -1;
+  const long total = (long)R * maps->C * PH * PW;
+  if (total <= 0) return 0;
+  roi_align_levels_fwd_kernel<<<grid_for(total), 256, 0, st>>>(*maps, rois, levels, out, R, PH, PW, sampling);
   HIP_LAUNCH_CHECK();
   return 0;
 }

@@ -412,6 +412,24 @@ int bigdl_nms(const float* boxes_sorted, int n, float thresh, int normalized, in
               unsigned long long* mask_ws, int* keep_out, int* count_out, hipStream_t st);
 int bigdl_roi_align_fwd(const float* x, const float* rois, float* out, int R, int rcols, int C, int H, int W,
                         int PH, int PW, float scale, int sampling, hipStream_t st);
+// Segmented greedy NMS: one workgroup per (image, class) of scores [R][C] / boxes [R][Cb][4] (Cb == C or 1); offsets =
+// B + 1 host row offsets. keep [R][C] uint8 is written in full; overflow[0] = 1 when a segment has more candidates
+// than the LDS capacity (cap: 0 = chosen from the longest image, else 256, 1024 or 4096). Returns the capacity used,
+// or < 0 on a bad argument.
+int bigdl_nms_classes(const float* scores, const float* boxes, unsigned char* keep, int* overflow,
+                      const int* offsets_host, int B, int C, int Cb, int skip_class, float score_thresh,
+                      int inclusive, int pre_topk, float nms_thresh, int normalized, int cap, hipStream_t st);
+// RoiAlign over up to 8 pyramid levels in one launch: rois [R][5] (batch index first), levels int32 [R]; both
+// indices are clamped to the maps that exist.
+#define BIGDL_ROI_MAX_LEVELS 8
+struct RoiLevelMaps {
+  const float* x[BIGDL_ROI_MAX_LEVELS];
+  int H[BIGDL_ROI_MAX_LEVELS], W[BIGDL_ROI_MAX_LEVELS];
+  float scale[BIGDL_ROI_MAX_LEVELS];
+  int L, N, C;
+};
+int bigdl_roi_align_levels_fwd(const RoiLevelMaps* maps, const float* rois, const int* levels, float* out, int R,
+                               int PH, int PW, int sampling, hipStream_t st);
 int bigdl_roi_pool_fwd(const float* x, const float* rois, float* out, int* argmax, int R, int C, int H, int W,
                        int PH, int PW, float scale, hipStream_t st);
 int bigdl_roi_pool_bwd(const float* gy, const int* argmax, const float* rois, float* gx, int R, int C, int H, int W,
