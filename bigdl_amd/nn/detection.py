@@ -12,7 +12,9 @@ run in HIP kernels (csrc/detection.hip) when the feature maps live on the GPU; t
 BoxPostProcessor, DetectionOutputFrcnn, DetectionOutputSSD and Pooler make one ``multiclass_nms`` /
 ``roi_align_levels`` call per forward (every class of every image, every pyramid level, in one launch) and select
 their outputs from the returned mask; ``ops.detection.set_batched(False)`` (BIGDL_DET_BATCHED=0,
-``bigdl.detection.batched``) and the CPU engine run the per-class / per-level loops. All boxes are fp32 —
+``bigdl.detection.batched``) and the CPU engine run the per-class / per-level loops. RegionProposal batches only when
+the switch is set explicitly (``set_batched(True)`` / BIGDL_DET_BATCHED=1): it then runs its head once per level on the
+whole batch and makes one ``rpn_select`` call (all images and levels in one launch per stage). All boxes are fp32 —
 box arithmetic is not a bandwidth problem and bf16 boxes would shift pixel coordinates.
 """
 import math
@@ -565,6 +567,12 @@ class ProposalPostProcessor(AbstractModule):
         raise NotImplementedError("ProposalPostProcessor only support inference")
 
 
+_ANCHOR_TABLES = {}      # RegionProposal._cached_anchors
+# RegionProposal on GPU tensors when the batching switch is unset: the measured gain at batch 1 did not exceed three
+# round-to-round spreads in every run (README, profiles/rpn_batched_ab.txt), so the batched route is opt-in
+RPN_BATCHED_DEFAULT = False
+
+
 class RegionProposal(Container):
     """FPN region proposal network (reference RegionProposal.scala:40). Input Table(features Table, image size
     (h, w)); output Table of per-image proposals (postNmsTopN, 4)."""
@@ -604,8 +612,44 @@ class RegionProposal(Container):
             res.append(self.anchors[i].generateAnchors(f.shape[3], f.shape[2], self.anchorStride[i], f.device))
         return res
 
+    def _cached_anchors(self, features):
+        """anchorGenerator with the tables kept per (level, H, W, device): nothing is regenerated or copied to the
+        device after the first forward of a shape. The tables depend on the constructor arguments alone, so the
+        cache is shared by all instances and stays out of clones and saved models."""
+        res = []
+        for i in range(min(len(self.anchorSizes), features.length())):
+            f = features[i + 1]
+            key = (tuple(self.aspectRatios), self.anchorSizes[i], self.anchorStride[i], f.shape[2], f.shape[3],
+                   str(f.device))
+            if key not in _ANCHOR_TABLES:
+                if len(_ANCHOR_TABLES) >= 64:                  # images of many sizes: start over
+                    _ANCHOR_TABLES.clear()
+                _ANCHOR_TABLES[key] = self.anchors[i].generateAnchors(f.shape[3], f.shape[2], self.anchorStride[i],
+                                                                      f.device)
+            res.append(_ANCHOR_TABLES[key])
+        return res
+
+    def _forward_batched(self, features, size):
+        """The head once per level on the whole batch, then D.rpn_select: one launch per stage for all images and
+        levels and one host synchronisation."""
+        anchors = self._cached_anchors(features)
+        sel = self.boxSelector
+        obj, reg = [], []
+        for i in range(len(anchors)):
+            ho = self.head.forward(features[i + 1])
+            obj.append(ho[1])
+            reg.append(ho[2])
+        pre = sel.preNmsTopNTrain if self.train else sel.preNmsTopNTest
+        post = self.postNmsTopNTrain if self.train else self.postNmsTopNTest
+        out = Table()
+        for b, boxes in enumerate(D.rpn_select(obj, reg, anchors, size, pre, post, sel.nmsThread)):
+            out[b + 1] = boxes
+        return out
+
     def updateOutput(self, input):
         features, size = input[1], input[2]
+        if D.batched(features[1].is_cuda, default=RPN_BATCHED_DEFAULT):
+            return self._forward_batched(features, size)
         anchors = self.anchorGenerator(features)
         self.boxSelector.train = self.train
         batch = features[1].shape[0]

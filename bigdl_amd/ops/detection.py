@@ -8,6 +8,7 @@ one-thread-per-output RoiAlign / RoiPooling; ``multiclass_nms`` and ``roi_align_
 images, or all pyramid levels, in one launch each); on the CPU the same arithmetic runs in numpy / torch. Box
 conventions follow the reference: pixel boxes use ``+1`` widths (``(x2 - x1 + 1)``) unless ``normalized``.
 """
+import collections
 import math
 import os
 
@@ -104,12 +105,14 @@ def nms_fast(scores, boxes, nms_thresh, score_thresh, topk=-1, eta=1.0, normaliz
 
 
 # ------------------------------------------------------------------------------- batched detection ops
-# multiclass_nms / roi_align_levels run every (image, class) segment, or every pyramid level, in one launch
-# (csrc/detection.hip nms_classes_kernel / roi_align_levels_fwd_kernel): BIGDL_DET_BATCHED / Engine property
-# bigdl.detection.batched / set_batched; unset means on for GPU tensors. Off, or on the CPU, the same results come
+# multiclass_nms / roi_align_levels / rpn_select run every (image, class) segment, every pyramid level, or every
+# (image, level) segment in one launch per stage (csrc/detection.hip nms_classes_kernel /
+# roi_align_levels_fwd_kernel / segmented_topk_*_kernel): BIGDL_DET_BATCHED / Engine property
+# bigdl.detection.batched / set_batched; unset means on for GPU tensors (for the RegionProposal module: off, it
+# batches only when the switch is set). Off, or on the CPU, the same results come
 # from the per-class / per-level loops below, which are also what an overflowing call falls back to.
 _BATCHED = [None]
-_ROUTE = {"multiclass_nms": None, "roi_align_levels": None, "last": None}
+_ROUTE = {"multiclass_nms": None, "roi_align_levels": None, "rpn_select": None, "last": None}
 NMS_CLASSES_MIN_CAP = 256                      # smallest LDS capacity nms_classes_kernel is instantiated for
 
 
@@ -118,17 +121,18 @@ def set_batched(v):
     _BATCHED[0] = None if v is None or v == "" else str(v).lower() in ("1", "true", "yes")
 
 
-def batched(is_cuda):
+def batched(is_cuda, default=True):
+    """Whether a caller with GPU tensors (``is_cuda``) batches; ``default`` is its answer when nothing is set."""
     v = _BATCHED[0]
     if v is None:
         env = os.environ.get("BIGDL_DET_BATCHED", "")
-        v = True if env == "" else env.lower() in ("1", "true", "yes")
+        v = default if env == "" else env.lower() in ("1", "true", "yes")
     return bool(v) and bool(is_cuda)
 
 
 def last_route(op=None):
-    """"batched", "loop" or "overflow": the path the last call of ``op`` ("multiclass_nms" / "roi_align_levels")
-    took; without ``op``, of whichever of the two ran last."""
+    """"batched", "loop" or "overflow": the path the last call of ``op`` ("multiclass_nms" / "roi_align_levels" /
+    "rpn_select") took; without ``op``, of whichever of them ran last."""
     return _ROUTE["last" if op is None else op]
 
 
@@ -241,6 +245,166 @@ def roi_align_levels(fmaps, rois5, levels, scales, sampling_ratio, res):
         return out
     _set_route("roi_align_levels", "loop")
     return _roi_align_levels_loop(fmaps, rois5, levels, scales, sampling_ratio, res)
+
+
+# ------------------------------------------------------------------------------------ segmented top-k
+TOPK_MAX_K = 4096                              # segmented_topk_*_kernel sorts at most this many elements in LDS
+TopK = collections.namedtuple("TopK", "indices values offsets counts regression anchors")
+
+
+def _stable_order(v):
+    """Indices of a stable descending sort: NaN first, -0.0 == +0.0, ties by lower index."""
+    return torch.sort(v, descending=True, stable=True).indices
+
+
+def _segmented_topk_cpu(values, offsets, k, mask, global_index):
+    out_off = _offsets(min(k, offsets[s + 1] - offsets[s]) for s in range(len(offsets) - 1))
+    idx = torch.zeros(out_off[-1], dtype=torch.int32)
+    val = torch.zeros(out_off[-1], dtype=torch.float32)
+    counts = torch.zeros(len(offsets) - 1, dtype=torch.int32)
+    for s in range(len(offsets) - 1):
+        lo, hi = offsets[s], offsets[s + 1]
+        seg = values[lo:hi]
+        cand = torch.arange(hi - lo) if mask is None else torch.nonzero(mask[lo:hi]).reshape(-1)
+        top = cand[_stable_order(seg[cand])[:k]]
+        n = top.numel()
+        idx[out_off[s]:out_off[s + 1]] = lo if global_index else 0
+        idx[out_off[s]:out_off[s] + n] = (top + (lo if global_index else 0)).int()
+        val[out_off[s]:out_off[s] + n] = seg[top]
+        counts[s] = n
+    return TopK(idx, val, out_off, counts if mask is not None else None, None, None)
+
+
+def segmented_topk(values, offsets=None, k=1, mask=None, regression=None, anchors=None, global_index=False):
+    """The first ``k`` (1 .. 4096) elements of every segment in the order of
+    ``torch.sort(seg, descending=True, stable=True)``: NaN first, then larger values with ``-0.0 == +0.0``, ties by
+    the lower index within the segment. One launch of csrc/detection.hip segmented_topk_*_kernel per 64 segments
+    (flat) or for all segments (level maps), one workgroup per segment, any segment length below 2^31.
+
+    Flat mode: ``values`` fp32 (R,), ``offsets`` the S + 1 monotone host offsets ending at R (empty segments
+    allowed), ``mask`` an optional uint8 / bool (R,) whose zeros exclude elements. Level-map mode: ``values`` is a
+    list of up to 8 objectness maps (N, A, H_l, W_l); segment (n, l) is image n of level l (image-major) and its
+    element index is ``(h * W_l + w) * A + a``; ``regression`` (N, 4A, H_l, W_l) and ``anchors`` (H_l W_l A, 4) per
+    level are gathered alongside.
+
+    Returns TopK(indices int32, values, offsets, counts, regression, anchors): segment s owns the output slots
+    ``offsets[s] : offsets[s] + min(k, len_s)`` in rank order; ``counts`` (int32 per segment, on the device) is given
+    only with a mask, whose segment fills ``counts[s]`` slots, the rest holding the segment's first index and value
+    0. Indices are relative to the segment, or into ``values`` with ``global_index`` (flat mode)."""
+    k = int(k)
+    assert 1 <= k <= TOPK_MAX_K, f"segmented_topk: k must be in 1 .. {TOPK_MAX_K}"
+    if isinstance(values, (list, tuple)):
+        obj = [o.float().contiguous() for o in values]
+        reg = [r.float().contiguous() for r in regression]
+        anc = [a.float().contiguous() for a in anchors]
+        N = obj[0].shape[0]
+        out_off = _offsets(min(k, o[0].numel()) for _ in range(N) for o in obj)
+        dev, S = obj[0].device, out_off[-1]
+        assert _on_gpu(obj[0]), "segmented_topk: the level-map mode runs on the GPU only"
+        idx = torch.empty(S, dtype=torch.int32, device=dev)
+        val = torch.empty(S, dtype=torch.float32, device=dev)
+        greg = torch.empty(S, 4, dtype=torch.float32, device=dev)
+        ganc = torch.empty(S, 4, dtype=torch.float32, device=dev)
+        native.get().segmented_topk_maps(obj, reg, anc, k, idx, val, greg, ganc)
+        return TopK(idx, val, out_off, None, greg, ganc)
+    off = [int(o) for o in offsets]
+    assert off[0] == 0 and off[-1] == values.numel(), "segmented_topk: offsets must start at 0 and end at R"
+    if mask is not None:
+        mask = mask.reshape(-1)
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    if not _on_gpu(values):
+        return _segmented_topk_cpu(values.float(), off, k, mask, global_index)
+    v = values.float().contiguous()
+    out_off = _offsets(min(k, off[s + 1] - off[s]) for s in range(len(off) - 1))
+    idx = torch.empty(out_off[-1], dtype=torch.int32, device=v.device)
+    val = torch.empty(out_off[-1], dtype=torch.float32, device=v.device)
+    counts = None if mask is None else torch.empty(len(off) - 1, dtype=torch.int32, device=v.device)
+    native.get().segmented_topk_flat(v, None if mask is None else mask.contiguous(), off, out_off, k,
+                                     bool(global_index), idx, val, counts)
+    return TopK(idx, val, out_off, counts, None, None)
+
+
+# ------------------------------------------------------------------------------------------ RPN selection
+def _rpn_clip(props, im_size):
+    """clip_boxes of (K, 4) proposals to im_size = (height, width); a device tensor is not read back."""
+    if torch.is_tensor(im_size) and _on_gpu(im_size):
+        hw = im_size.reshape(-1).float()
+        props[:, 0::2] = torch.minimum(props[:, 0::2].clamp_min(0), hw[1] - 1)
+        props[:, 1::2] = torch.minimum(props[:, 1::2].clamp_min(0), hw[0] - 1)
+        return props
+    hw = im_size.reshape(-1) if torch.is_tensor(im_size) else im_size
+    clip_boxes(props, float(hw[0]), float(hw[1]))
+    return props
+
+
+def _rpn_select_loop(objectness, regression, anchors, im_size, pre_topk, post_topk, nms_thresh):
+    out = []
+    for b in range(objectness[0].shape[0]):
+        boxes, logits = [], []
+        for obj, reg, anc in zip(objectness, regression, anchors):
+            _, A, H, W = obj.shape
+            o = obj[b].float().permute(1, 2, 0).reshape(-1)                               # (h, w, a)
+            r = reg[b].float().reshape(A, 4, H, W).permute(2, 3, 0, 1).reshape(-1, 4)
+            order = _stable_order(o)[:pre_topk]
+            props = _rpn_clip(bbox_transform_inv(anc.to(r.device).float()[order], r[order], normalized=True), im_size)
+            keep = nms_sorted(props, nms_thresh)
+            boxes.append(props[keep])
+            logits.append(o[order][keep])
+        allb, alls = torch.cat(boxes), torch.cat(logits)
+        out.append(allb[_stable_order(alls)[:post_topk]])
+    return out
+
+
+def rpn_nms_launch(props, offsets, nms_thresh):
+    """Greedy NMS (pixel ``+1`` areas) of ranked boxes: props fp32 (R, 4) on the GPU, every segment
+    ``offsets[s] : offsets[s + 1]`` (at most 4096 rows, fewer than 2^24 rows in all) already in rank order. One
+    nms_classes_kernel launch with C = Cb = 1 and a descending ramp as scores, so the kernel's own sort keeps the
+    rank order whatever the values the ranking came from (NaN included). Returns the uint8 (R,) keep mask."""
+    R = props.shape[0]
+    assert R < (1 << 24) and all(b - a <= TOPK_MAX_K for a, b in zip(offsets, offsets[1:]))
+    ramp = torch.arange(R, 0, -1, dtype=torch.float32, device=props.device).reshape(R, 1)
+    keep = torch.empty(R, 1, dtype=torch.uint8, device=props.device)
+    overflow = torch.empty(1, dtype=torch.int32, device=props.device)   # a segment fits the capacity: never set
+    nms_classes_launch(ramp, props.float().contiguous().reshape(R, 1, 4), offsets, 0.0, nms_thresh, -1, True, -1,
+                       False, keep, overflow)
+    return keep.reshape(R)
+
+
+def rpn_select(objectness, regression, anchors, im_size, pre_topk, post_topk, nms_thresh):
+    """FPN proposal selection for a whole batch. Per level l: ``objectness[l]`` (N, A, H_l, W_l) raw logits,
+    ``regression[l]`` (N, 4A, H_l, W_l), ``anchors[l]`` (H_l W_l A, 4) in (h, w, a) order; ``im_size`` = (height,
+    width). Per image and level the ``pre_topk`` best anchors are decoded (``bbox_transform_inv(normalized=True)``),
+    clipped and suppressed greedily at ``nms_thresh`` (pixel ``+1`` areas); the ``post_topk`` best survivors of all
+    levels of an image are its proposals. Returns the list of per-image (K_n, 4) boxes.
+
+    Ranking is on the logits, in the order of ``segmented_topk``: a stable descending sort, ties by lower anchor
+    index, then by level. ``RegionProposal``'s per-image loop ranks ``sigmoid(logit)`` with ``torch.topk``; sigmoid
+    is monotone, so the two agree wherever fp32 sigmoid keeps the values apart, and where it collapses them (it
+    saturates near 1) the loop's order is ``torch.topk``'s unspecified tie order, which this op replaces by the
+    defined one. Only boxes are returned, so no sigmoid is evaluated.
+
+    On the GPU with batching on (at most 8 levels, ``pre_topk`` / ``post_topk`` at most 4096) this is one level-map
+    ``segmented_topk`` launch, one decode, one ``nms_classes_kernel`` launch with a segment per (image, level) and a
+    descending ramp as scores, one flat ``segmented_topk`` launch over the kept rows, one read of the per-image
+    counts (the only synchronisation) and one gather. Otherwise the same pipeline runs segment by segment with
+    ``torch.sort(stable=True)`` and ``nms_sorted``; the two forms are bit-equal."""
+    objectness, regression, anchors = list(objectness), list(regression), list(anchors)
+    L, N = len(objectness), objectness[0].shape[0]
+    pre_topk, post_topk = int(pre_topk), int(post_topk)
+    assert L == len(regression) == len(anchors) and pre_topk >= 1 and post_topk >= 1
+    if not (batched(_on_gpu(objectness[0])) and L <= 8 and pre_topk <= TOPK_MAX_K and post_topk <= TOPK_MAX_K
+            and N * L < 4096):                               # rpn_nms_launch: fewer than 2^24 rows
+        _set_route("rpn_select", "loop")
+        return _rpn_select_loop(objectness, regression, anchors, im_size, pre_topk, post_topk, nms_thresh)
+    dev = objectness[0].device
+    top = segmented_topk(objectness, k=pre_topk, regression=regression, anchors=[a.to(dev) for a in anchors])
+    props = _rpn_clip(bbox_transform_inv(top.anchors, top.regression, normalized=True), im_size)
+    keep = rpn_nms_launch(props, top.offsets, nms_thresh)
+    fin = segmented_topk(top.values, top.offsets[::L], post_topk, mask=keep, global_index=True)
+    counts = fin.counts.tolist()
+    rows = props[fin.indices.long()]
+    _set_route("rpn_select", "batched")
+    return [rows[fin.offsets[b]:fin.offsets[b] + counts[b]] for b in range(N)]
 
 
 # ------------------------------------------------------------------------------------------- RoiAlign

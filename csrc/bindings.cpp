@@ -1137,6 +1137,90 @@ void roi_align_levels_fwd(std::vector<Tensor> fmaps, const Tensor& rois, const T
   TORCH_CHECK(rc == 0, "roi_align_levels failed");
 }
 
+static void check_i32(const Tensor& t, int64_t n, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kInt && t.numel() >= n, what,
+              ": contiguous int32 device tensor of at least ", n, " elements");
+}
+
+// values fp32 [R]; mask uint8 [R] or an undefined tensor; in_off / out_off = S + 1 host offsets (out_off[s + 1] -
+// out_off[s] == min(k, len_s)); out_idx int32 / out_val fp32 [out_off[S]]; counts int32 [S] or undefined.
+void segmented_topk_flat(const Tensor& values, const c10::optional<Tensor>& mask, std::vector<int64_t> in_off,
+                         std::vector<int64_t> out_off, int64_t k, bool global_index, const Tensor& out_idx,
+                         const Tensor& out_val, const c10::optional<Tensor>& counts) {
+  check_f32(values, "segmented_topk values"); check_f32(out_val, "segmented_topk out_val");
+  TORCH_CHECK(values.dim() == 1 && values.numel() < (int64_t(1) << 31), "segmented_topk: values [R], R < 2^31");
+  TORCH_CHECK(k >= 1 && k <= 4096, "segmented_topk: 1 <= k <= 4096");
+  TORCH_CHECK(in_off.size() >= 1 && in_off.size() == out_off.size() && in_off.front() == 0 &&
+                  in_off.back() == values.numel() && out_off.front() == 0,
+              "segmented_topk: offsets must start at 0 and end at R");
+  const int64_t S = (int64_t)in_off.size() - 1;
+  std::vector<int> io(S + 1), oo(S + 1);
+  for (int64_t s = 0; s <= S; ++s) {
+    TORCH_CHECK(s == 0 || in_off[s] >= in_off[s - 1], "segmented_topk: offsets must be monotone");
+    TORCH_CHECK(s == 0 || out_off[s] - out_off[s - 1] == std::min<int64_t>(k, in_off[s] - in_off[s - 1]),
+                "segmented_topk: a segment owns min(k, len) output slots");
+    io[s] = (int)in_off[s]; oo[s] = (int)out_off[s];
+  }
+  check_i32(out_idx, out_off.back(), "segmented_topk out_idx");
+  TORCH_CHECK(out_val.numel() >= out_off.back(), "segmented_topk: out_val too short");
+  const unsigned char* mp = nullptr;
+  if (mask.has_value() && mask->defined()) {
+    TORCH_CHECK(mask->is_cuda() && mask->is_contiguous() && mask->scalar_type() == at::kByte &&
+                    mask->numel() == values.numel(), "segmented_topk: mask must be a contiguous uint8 [R]");
+    mp = mask->data_ptr<uint8_t>();
+  }
+  int* cp = nullptr;
+  if (counts.has_value() && counts->defined()) {
+    check_i32(*counts, S, "segmented_topk counts");
+    cp = counts->data_ptr<int>();
+  }
+  if (S == 0) return;
+  const int rc = bigdl_segmented_topk_flat(values.data_ptr<float>(), mp, io.data(), oo.data(), (int)S, (int)k,
+                                           global_index ? 1 : 0, out_idx.data_ptr<int>(), out_val.data_ptr<float>(),
+                                           cp, stream());
+  TORCH_CHECK(rc == 0, "segmented_topk failed");
+}
+
+// obj[l] [N, A, H_l, W_l], reg[l] [N, 4A, H_l, W_l], anc[l] [H_l W_l A, 4]; the outputs have
+// N * sum_l min(k, H_l W_l A) slots, image-major then level then rank.
+void segmented_topk_maps(std::vector<Tensor> obj, std::vector<Tensor> reg, std::vector<Tensor> anc, int64_t k,
+                         const Tensor& out_idx, const Tensor& out_val, const Tensor& out_reg, const Tensor& out_anc) {
+  const int64_t L = (int64_t)obj.size();
+  TORCH_CHECK(L >= 1 && L <= BIGDL_ROI_MAX_LEVELS && (int64_t)reg.size() == L && (int64_t)anc.size() == L,
+              "segmented_topk_maps: 1 to 8 levels, one objectness, regression and anchor tensor each");
+  TORCH_CHECK(k >= 1 && k <= 4096, "segmented_topk_maps: 1 <= k <= 4096");
+  TopkLevelMaps maps{};
+  maps.L = (int)L; maps.N = (int)obj[0].size(0); maps.A = (int)obj[0].size(1);
+  int64_t per_image = 0;
+  for (int64_t l = 0; l < L; ++l) {
+    check_f32(obj[l], "segmented_topk_maps objectness"); check_f32(reg[l], "segmented_topk_maps regression");
+    check_f32(anc[l], "segmented_topk_maps anchors");
+    TORCH_CHECK(obj[l].dim() == 4 && obj[l].size(0) == maps.N && obj[l].size(1) == maps.A && maps.N >= 1 &&
+                    maps.A >= 1, "segmented_topk_maps: objectness [N, A, H, W] with the same N and A on every level");
+    const int64_t H = obj[l].size(2), W = obj[l].size(3);
+    TORCH_CHECK(H >= 1 && W >= 1 && H * W * maps.A < (int64_t(1) << 31), "segmented_topk_maps: level size");
+    TORCH_CHECK(reg[l].dim() == 4 && reg[l].size(0) == maps.N && reg[l].size(1) == 4 * maps.A &&
+                    reg[l].size(2) == H && reg[l].size(3) == W, "segmented_topk_maps: regression [N, 4A, H, W]");
+    TORCH_CHECK(anc[l].dim() == 2 && anc[l].size(0) == H * W * maps.A && anc[l].size(1) == 4,
+                "segmented_topk_maps: anchors [H W A, 4]");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(anc[l].data_ptr()) % 16 == 0, "segmented_topk_maps: anchors alignment");
+    maps.obj[l] = obj[l].data_ptr<float>(); maps.reg[l] = reg[l].data_ptr<float>();
+    maps.anc[l] = anc[l].data_ptr<float>(); maps.HW[l] = (int)(H * W);
+    per_image += std::min<int64_t>(k, H * W * maps.A);
+  }
+  const int64_t slots = per_image * maps.N;
+  check_i32(out_idx, slots, "segmented_topk_maps out_idx");
+  check_f32(out_val, "segmented_topk_maps out_val"); check_f32(out_reg, "segmented_topk_maps out_reg");
+  check_f32(out_anc, "segmented_topk_maps out_anc");
+  TORCH_CHECK(out_val.numel() >= slots && out_reg.numel() >= 4 * slots && out_anc.numel() >= 4 * slots,
+              "segmented_topk_maps: outputs too short");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out_reg.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(out_anc.data_ptr()) % 16 == 0, "segmented_topk_maps: output alignment");
+  const int rc = bigdl_segmented_topk_maps(&maps, (int)k, out_idx.data_ptr<int>(), out_val.data_ptr<float>(),
+                                           out_reg.data_ptr<float>(), out_anc.data_ptr<float>(), stream());
+  TORCH_CHECK(rc == 0, "segmented_topk_maps failed");
+}
+
 void roi_pool_fwd(const Tensor& x, const Tensor& rois, const Tensor& out, const Tensor& argmax, double scale) {
   check_f32(x, "roi_pool x"); check_f32(rois, "roi_pool rois"); check_f32(out, "roi_pool out");
   TORCH_CHECK(x.dim() == 4 && rois.dim() == 2 && rois.size(1) == 5 && out.dim() == 4 && out.size(0) == rois.size(0) &&
@@ -1927,6 +2011,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("score_thresh"), py::arg("inclusive"), py::arg("pre_topk"), py::arg("nms_thresh"),
         py::arg("normalized"), py::arg("keep"), py::arg("overflow"), py::arg("cap") = 0);
   m.def("roi_align_levels_fwd", &roi_align_levels_fwd);
+  m.def("segmented_topk_flat", &segmented_topk_flat);
+  m.def("segmented_topk_maps", &segmented_topk_maps);
   m.def("roi_pool_fwd", &roi_pool_fwd);
   m.def("roi_pool_bwd", &roi_pool_bwd);
   m.def("lrn_fwd", &lrn_fwd);

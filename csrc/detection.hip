@@ -1,7 +1,9 @@
 // Detection kernels for gfx950: greedy NMS (64-bit IoU masks + single-wave scan), segmented NMS over every
 // (image, class) column of a score matrix in one launch (nms_classes_kernel: threshold, sort, top-k cut and greedy
-// pass in LDS, one workgroup per segment), RoiAlign forward for one map or for all pyramid levels in one launch
-// (roi_align_levels_fwd_kernel; both call roi_align_bin), RoiPooling forward/backward.
+// pass in LDS, one workgroup per segment), segmented top-k in the order of a stable descending sort over segments of
+// any length (segmented_topk_flat_kernel / segmented_topk_maps_kernel: radix select, ordered compaction, bitonic sort
+// of at most 4096 survivors, one workgroup per segment), RoiAlign forward for one map or for all pyramid levels in
+// one launch (roi_align_levels_fwd_kernel; both call roi_align_bin), RoiPooling forward/backward.
 //
 // Reference semantics: S/nn/Nms.scala:50-236 (greedy NMS over score-sorted boxes, "IoU > thresh" suppresses,
 // pixel areas (x2-x1+1)(y2-y1+1) unless normalized), S/nn/RoiAlign.scala:45-420 (bilinear sampling grid,
@@ -189,6 +191,281 @@ __global__ void __launch_bounds__(256) nms_classes_kernel(const float* __restric
     if (alive[t]) keep[(size_t)(row0 + key_r[t]) * C + c] = 1;
 }
 
+// ------------------------------------------------------------------------------------------- segmented top-k
+// One 1024-thread workgroup per segment returns the first k elements of the order of a stable descending sort
+// (torch.sort(descending=True, stable=True)): NaN first, then larger values, -0.0 == +0.0, ties by lower index.
+// topk_sel_key maps a float to a 32-bit key that is larger for an element that comes first and equal exactly for
+// elements the order ties. A radix select over the key (four 8-bit digits, an integer histogram in LDS, the segment
+// re-read per pass) finds the cut key T and the number of keys above it; one pass in index order then puts every
+// key above T into LDS and writes the first k - above elements equal to T straight behind them in the output
+// (ballot + popcount ranks, as nms_classes_kernel compacts); a bitonic sort on (key, index) orders the at most
+// k - 1 <= 4095 elements above T. No global workspace, integer LDS atomics only, every loop bounded by the segment
+// length, and an output slot past the segment's count is filled with index 0 / value 0 without reading anything.
+constexpr int TOPK_THREADS = 1024;
+constexpr int TOPK_WAVES = TOPK_THREADS / 64;
+constexpr int TOPK_UNROLL = 4;         // elements per thread and loop trip
+constexpr int TOPK_MAX_K = 4096;
+constexpr int TOPK_MAX_SEGMENTS = 64;   // flat mode: offsets travel by value, one launch per 64 segments
+struct TopkOffsets { int in[TOPK_MAX_SEGMENTS + 1]; int out[TOPK_MAX_SEGMENTS + 1]; };
+
+__device__ __forceinline__ unsigned topk_sel_key(float v) {
+  if (v != v) return 0xffffffffu;                       // every NaN is the same, largest key
+  if (v == 0.f) return 0x80000000u;                     // -0.0 and +0.0 tie
+  const unsigned b = __float_as_uint(v);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);    // +inf is 0xff800000, -inf 0x007fffff
+}
+
+// Flat mode: element i of the segment is values[in0 + i], skipped when mask[in0 + i] == 0.
+struct TopkFlatLoader {
+  const float* values;
+  const unsigned char* mask;
+  __device__ __forceinline__ bool load(unsigned i, float& v) const {
+    v = values[i];
+    return mask == nullptr || mask[i] != 0;
+  }
+};
+// Level-map mode: element i = (h * W + w) * A + a of image n is obj[n][a][h][w].
+struct TopkMapLoader {
+  const float* obj;    // map of this image: [A][HW]
+  int A, HW;
+  __device__ __forceinline__ bool load(unsigned i, float& v) const {
+    const unsigned hw = i / (unsigned)A, a = i - hw * (unsigned)A;
+    v = obj[(size_t)a * HW + hw];
+    return true;
+  }
+};
+
+// The body both modes share. len = segment length, k >= 1; out_idx / out_val point at the segment's first output
+// slot and have min(k, len) slots. Returns the number of slots written in rank order (workgroup-uniform); key_s /
+// idx_s then hold nothing the caller needs: the ranked indices are in out_idx.
+template <class Loader>
+__device__ int topk_segment(const Loader& ld, unsigned len, int k, int idx_base, int* out_idx,
+                            unsigned* key_s, int* idx_s, int* hist, int* wave_cnt, int* sel) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int slots = (int)min((unsigned)k, len);
+  // ---- radix select: after pass p the top 8 * (p + 1) bits of T are in `prefix`, `above` counts keys over them
+  unsigned prefix = 0;
+  int above = 0, want = 0;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    for (int t = tid; t < 256; t += TOPK_THREADS) hist[t] = 0;
+    __syncthreads();
+    for (unsigned base = 0; base < len; base += TOPK_THREADS * TOPK_UNROLL) {
+      bool p[TOPK_UNROLL];
+      unsigned key[TOPK_UNROLL];
+#pragma unroll
+      for (int j = 0; j < TOPK_UNROLL; ++j) {             // the loads of one trip are independent: all in flight
+        const unsigned i = base + j * TOPK_THREADS + tid;
+        p[j] = false;
+        key[j] = 0;
+        if (i < len) {
+          float v;
+          p[j] = ld.load(i, v);
+          key[j] = topk_sel_key(v);
+          p[j] = p[j] && (pass == 0 || (key[j] >> (shift + 8)) == prefix);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < TOPK_UNROLL; ++j) {
+        const unsigned long long m = __ballot(p[j]);
+        if (m == 0ull) continue;                          // wave-uniform
+        const int digit = (int)((key[j] >> shift) & 0xffu);
+        const int d0 = __shfl(digit, __ffsll((long long)m) - 1, 64);
+        const unsigned long long same = __ballot(p[j] && digit == d0);
+        if (p[j] && digit != d0) atomicAdd(&hist[digit], 1);
+        if (lane == 0) atomicAdd(&hist[d0], __popcll(same));   // the common digit of the wave in one add
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {                                    // lane l owns digits 255 - 4l .. 252 - 4l, largest first
+      int c[4], s = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { c[j] = hist[255 - (4 * lane + j)]; s += c[j]; }
+      int incl = s;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+      }
+      if (pass == 0) {                                  // the histogram of pass 0 counts every valid element
+        const int valid = __shfl(incl, 63, 64);
+        if (lane == 0) sel[2] = min(k, valid);
+        want = min(k, valid);
+      } else {
+        want = sel[2];
+      }
+      int run = above + incl - s;
+      if (want > 0 && run < want && want <= run + s) {  // exactly one lane holds the cut
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (run < want && want <= run + c[j]) { sel[0] = 255 - (4 * lane + j); sel[1] = run; }
+          run += c[j];
+        }
+      }
+    }
+    __syncthreads();
+    want = sel[2];
+    if (want == 0) break;                               // nothing valid: workgroup-uniform
+    prefix = (prefix << 8) | (unsigned)sel[0];
+    above = sel[1];
+    __syncthreads();                                    // sel and hist are rewritten by the next pass
+  }
+  if (want == 0) {
+    for (int t = tid; t < slots; t += TOPK_THREADS) out_idx[t] = idx_base;
+    return 0;
+  }
+  // ---- compaction in index order: keys above T to LDS slots [0, above), the first want - above keys equal to T
+  //      to output slots [above, want)
+  const unsigned T = prefix;
+  const int need_eq = want - above;
+  int n_gt = 0, n_eq = 0;                               // workgroup-uniform running counts
+  for (unsigned base = 0; base < len; base += TOPK_THREADS * TOPK_UNROLL) {
+    bool gt[TOPK_UNROLL], eq[TOPK_UNROLL];
+    unsigned key[TOPK_UNROLL];
+    unsigned long long mg[TOPK_UNROLL], me[TOPK_UNROLL];
+#pragma unroll
+    for (int j = 0; j < TOPK_UNROLL; ++j) {
+      const unsigned i = base + j * TOPK_THREADS + tid;
+      gt[j] = eq[j] = false;
+      key[j] = 0;
+      if (i < len) {
+        float v;
+        const bool p = ld.load(i, v);
+        key[j] = topk_sel_key(v);
+        gt[j] = p && key[j] > T;
+        eq[j] = p && key[j] == T;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < TOPK_UNROLL; ++j) {               // sub-chunk j, wave w: counts at wave_cnt[2 (j W + w)]
+      mg[j] = __ballot(gt[j]);
+      me[j] = __ballot(eq[j]);
+      if (lane == 0) {
+        wave_cnt[2 * (j * TOPK_WAVES + wave)] = __popcll(mg[j]);
+        wave_cnt[2 * (j * TOPK_WAVES + wave) + 1] = __popcll(me[j]);
+      }
+    }
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int j = 0; j < TOPK_UNROLL; ++j) {               // index order: sub-chunk, then wave, then lane
+      int pg = n_gt + __popcll(mg[j] & below), pe = n_eq + __popcll(me[j] & below);
+      int tg = 0, te = 0;
+      for (int w = 0; w < TOPK_WAVES; ++w) {
+        const int cg = wave_cnt[2 * (j * TOPK_WAVES + w)], ce = wave_cnt[2 * (j * TOPK_WAVES + w) + 1];
+        if (w < wave) { pg += cg; pe += ce; }
+        tg += cg; te += ce;
+      }
+      const int i = (int)(base + j * TOPK_THREADS + tid);
+      if (gt[j] && pg < above) { key_s[pg] = key[j]; idx_s[pg] = i; }   // pg < above < k <= TOPK_MAX_K always
+      if (eq[j] && pe < need_eq) out_idx[above + pe] = idx_base + i;
+      n_gt += tg; n_eq += te;
+    }
+    __syncthreads();
+    if (n_gt >= above && n_eq >= need_eq) break;        // uniform: everything selected has been seen
+  }
+  // ---- bitonic sort of the keys above T: larger key first, lower index first among equal keys
+  int P = 2;
+  while (P < above) P <<= 1;                            // above < k <= 4096, so P <= 4096
+  for (int t = above + tid; t < P; t += TOPK_THREADS) { key_s[t] = 0u; idx_s[t] = 0x7fffffff; }
+  __syncthreads();
+  if (above > 1) {
+    for (int size = 2; size <= P; size <<= 1) {
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int t = tid; t < P / 2; t += TOPK_THREADS) {
+          const int lo = 2 * t - (t & (stride - 1));
+          const int hi = lo + stride;
+          const bool up = (lo & size) == 0;
+          const unsigned ka = key_s[lo], kb = key_s[hi];
+          const int ia = idx_s[lo], ib = idx_s[hi];
+          const bool after = ka < kb || (ka == kb && ia > ib);   // a belongs behind b
+          if (after == up) {
+            key_s[lo] = kb; key_s[hi] = ka;
+            idx_s[lo] = ib; idx_s[hi] = ia;
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+  for (int t = tid; t < above; t += TOPK_THREADS) out_idx[t] = idx_base + idx_s[t];
+  for (int t = want + tid; t < slots; t += TOPK_THREADS) out_idx[t] = idx_base;
+  __syncthreads();                                      // out_idx of this segment is read back by the caller
+  return want;
+}
+
+#define TOPK_SHARED                                                                                               \
+  __shared__ unsigned key_s[TOPK_MAX_K];                                                                          \
+  __shared__ int idx_s[TOPK_MAX_K];                                                                               \
+  __shared__ int hist[256];                                                                                       \
+  __shared__ int wave_cnt[2 * TOPK_WAVES * TOPK_UNROLL];                                                          \
+  __shared__ int sel[3]
+
+// values [R], mask uint8 [R] or null; segment s of this launch is [offs.in[s], offs.in[s + 1]), its output slots
+// start at offs.out[s]. out_idx holds indices within the segment (global_index: into values), counts [S] or null.
+__global__ void __launch_bounds__(TOPK_THREADS) segmented_topk_flat_kernel(const float* __restrict__ values,
+                                                                            const unsigned char* __restrict__ mask,
+                                                                            TopkOffsets offs, int k, int global_index,
+                                                                            int* __restrict__ out_idx,
+                                                                            float* __restrict__ out_val,
+                                                                            int* __restrict__ counts) {
+  TOPK_SHARED;
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const int in0 = offs.in[s];
+  const unsigned len = (unsigned)(offs.in[s + 1] - in0);
+  if (len == 0) {
+    if (counts != nullptr && tid == 0) counts[s] = 0;
+    return;
+  }
+  const TopkFlatLoader ld{values + in0, mask == nullptr ? nullptr : mask + in0};
+  int* oi = out_idx + offs.out[s];
+  float* ov = out_val + offs.out[s];
+  const int base = global_index ? in0 : 0;
+  const int n = topk_segment(ld, len, k, base, oi, key_s, idx_s, hist, wave_cnt, sel);
+  const int slots = (int)min((unsigned)k, len);
+  for (int t = tid; t < slots; t += TOPK_THREADS) ov[t] = t < n ? ld.values[oi[t] - base] : 0.f;
+  if (counts != nullptr && tid == 0) counts[s] = n;
+}
+
+// Segment (n, l) = blockIdx.x: image n of level l, n-major. Output slots of image n, level l start at
+// n * sum_l min(k, HW_l * A) + sum_{l' < l} min(k, HW_l' * A). out_reg / out_anc [slots][4] receive channels
+// 4a .. 4a + 3 at (h, w) of reg_l [N][4A][H][W] and row i of the level's anchors [HW * A][4].
+__global__ void __launch_bounds__(TOPK_THREADS) segmented_topk_maps_kernel(TopkLevelMaps maps, int k,
+                                                                            int* __restrict__ out_idx,
+                                                                            float* __restrict__ out_val,
+                                                                            float* __restrict__ out_reg,
+                                                                            float* __restrict__ out_anc) {
+  TOPK_SHARED;
+  const int n = blockIdx.x / maps.L, l = blockIdx.x % maps.L, tid = threadIdx.x;
+  const int A = maps.A, HW = maps.HW[l];
+  int per_image = 0, before = 0;
+  for (int j = 0; j < maps.L; ++j) {
+    const int sl = (int)min((unsigned)k, (unsigned)maps.HW[j] * (unsigned)A);
+    if (j < l) before += sl;
+    per_image += sl;
+  }
+  const size_t out0 = (size_t)n * per_image + before;
+  const unsigned len = (unsigned)HW * (unsigned)A;
+  const TopkMapLoader ld{maps.obj[l] + (size_t)n * A * HW, A, HW};
+  int* oi = out_idx + out0;
+  const int cnt = topk_segment(ld, len, k, 0, oi, key_s, idx_s, hist, wave_cnt, sel);   // == min(k, len)
+  const float* reg = maps.reg[l] + (size_t)n * 4 * A * HW;
+  const float* anc = maps.anc[l];
+  for (int t = tid; t < cnt; t += TOPK_THREADS) {
+    const unsigned i = (unsigned)oi[t];
+    const unsigned hw = i / (unsigned)A, a = i - hw * (unsigned)A;
+    float v;
+    ld.load(i, v);
+    out_val[out0 + t] = v;
+    float4 r;
+    r.x = reg[(size_t)(4 * a + 0) * HW + hw]; r.y = reg[(size_t)(4 * a + 1) * HW + hw];
+    r.z = reg[(size_t)(4 * a + 2) * HW + hw]; r.w = reg[(size_t)(4 * a + 3) * HW + hw];
+    reinterpret_cast<float4*>(out_reg)[out0 + t] = r;
+    reinterpret_cast<float4*>(out_anc)[out0 + t] = reinterpret_cast<const float4*>(anc)[i];
+  }
+}
+#undef TOPK_SHARED
+
 // ---------------------------------------------------------------------------------------------- RoiAlign
 // One output bin (ph, pw) of one roi on one channel plane xc [H][W]; rb = (x1, y1, x2, y2).
 __device__ __forceinline__ float roi_align_bin(const float* __restrict__ xc, const float* __restrict__ rb, int H,
@@ -364,6 +641,38 @@ int bigdl_roi_align_levels_fwd(const RoiLevelMaps* maps, const float* rois, cons
   const long total = (long)R * maps->C * PH * PW;
   if (total <= 0) return 0;
   roi_align_levels_fwd_kernel<<<grid_for(total), 256, 0, st>>>(*maps, rois, levels, out, R, PH, PW, sampling);
+  HIP_LAUNCH_CHECK();
+  return 0;
+}
+
+int bigdl_segmented_topk_flat(const float* values, const unsigned char* mask, const int* in_off_host,
+                              const int* out_off_host, int S, int k, int global_index, int* out_idx, float* out_val,
+                              int* counts, hipStream_t st) {
+  if (S < 0 || k < 1 || k > TOPK_MAX_K) return -1;
+  for (int s = 0; s < S; ++s) {
+    const long len = (long)in_off_host[s + 1] - in_off_host[s];
+    if (len < 0 || in_off_host[s] < 0) return -1;
+    if (out_off_host[s + 1] - out_off_host[s] != (int)std::min<long>(k, len)) return -1;
+  }
+  for (int s0 = 0; s0 < S; s0 += TOPK_MAX_SEGMENTS) {
+    const int ns = std::min(TOPK_MAX_SEGMENTS, S - s0);
+    TopkOffsets offs{};
+    for (int s = 0; s <= ns; ++s) { offs.in[s] = in_off_host[s0 + s]; offs.out[s] = out_off_host[s0 + s]; }
+    segmented_topk_flat_kernel<<<ns, TOPK_THREADS, 0, st>>>(values, mask, offs, k, global_index, out_idx, out_val,
+                                                            counts == nullptr ? nullptr : counts + s0);
+    HIP_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+int bigdl_segmented_topk_maps(const TopkLevelMaps* maps, int k, int* out_idx, float* out_val, float* out_reg,
+                              float* out_anc, hipStream_t st) {
+  if (maps->L < 1 || maps->L > BIGDL_ROI_MAX_LEVELS || maps->N < 1 || maps->A < 1 || k < 1 || k > TOPK_MAX_K)
+    return -1;
+  for (int l = 0; l < maps->L; ++l)
+    if (maps->HW[l] < 1 || (long)maps->HW[l] * maps->A >= (1l << 31)) return -1;
+  segmented_topk_maps_kernel<<<maps->N * maps->L, TOPK_THREADS, 0, st>>>(*maps, k, out_idx, out_val, out_reg,
+                                                                         out_anc);
   HIP_LAUNCH_CHECK();
   return 0;
 }

@@ -430,6 +430,24 @@ struct RoiLevelMaps {
 };
 int bigdl_roi_align_levels_fwd(const RoiLevelMaps* maps, const float* rois, const int* levels, float* out, int R,
                                int PH, int PW, int sampling, hipStream_t st);
+// Segmented top-k in the order of a stable descending sort (NaN first, -0.0 == +0.0, ties by lower index),
+// 1 <= k <= 4096, one workgroup per segment. Flat mode: values [R], mask uint8 [R] or null, S + 1 host offsets into
+// values and S + 1 into the outputs (segment s owns min(k, len_s) slots); out_idx is relative to the segment unless
+// global_index; counts [S] or null. Slots past a segment's count hold its first index and value 0.
+int bigdl_segmented_topk_flat(const float* values, const unsigned char* mask, const int* in_off_host,
+                              const int* out_off_host, int S, int k, int global_index, int* out_idx, float* out_val,
+                              int* counts, hipStream_t st);
+// Level-map mode: segment (n, l) is image n of obj[l] [N][A][H_l][W_l] in (h, w, a) order; besides indices and
+// values it gathers the rows of reg[l] [N][4A][H_l][W_l] and anc[l] [H_l W_l A][4] into out_reg / out_anc [slots][4].
+struct TopkLevelMaps {
+  const float* obj[BIGDL_ROI_MAX_LEVELS];
+  const float* reg[BIGDL_ROI_MAX_LEVELS];
+  const float* anc[BIGDL_ROI_MAX_LEVELS];
+  int HW[BIGDL_ROI_MAX_LEVELS];
+  int L, N, A;
+};
+int bigdl_segmented_topk_maps(const TopkLevelMaps* maps, int k, int* out_idx, float* out_val, float* out_reg,
+                              float* out_anc, hipStream_t st);
 int bigdl_roi_pool_fwd(const float* x, const float* rois, float* out, int* argmax, int R, int C, int H, int W,
                        int PH, int PW, float scale, hipStream_t st);
 int bigdl_roi_pool_bwd(const float* gy, const int* argmax, const float* rois, float* gx, int R, int C, int H, int W,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """A/B of the detection post-processing modules with batching off / on (BIGDL_DET_BATCHED 0 / 1: the per-class /
-per-level loops against one ``multiclass_nms`` / ``roi_align_levels`` launch, csrc/detection.hip).
+per-level loops against one ``multiclass_nms`` / ``roi_align_levels`` launch, and RegionProposal's per-image, per-level
+loop against ``rpn_select``'s one launch per stage, csrc/detection.hip).
 
   python tools/bench_detection.py              ms per forward of both paths, alternating in one process
   python tools/bench_detection.py --trace      also: kernel launches of one forward per path, each from a
@@ -26,7 +27,9 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
-CASES = ["boxpost1", "boxpost2", "pooler7", "pooler14", "ssd"]
+CASES = ["boxpost1", "boxpost2", "pooler7", "pooler14", "ssd", "rpn1", "rpn2", "rpn1stub", "rpn2stub"]
+OWN_KERNELS = ("nms_classes_kernel", "roi_align_levels_fwd_kernel", "segmented_topk_maps_kernel",
+               "segmented_topk_flat_kernel")
 
 
 def parse():
@@ -96,6 +99,31 @@ def make(case):
         return (lambda: m.forward(inp)), (f"DetectionOutputSSD {B} images x {nP} priors x {C} classes, confThresh 0.01, "
                                           f"nmsTopk 400, keepTopK 200; {float(cand):.0f} candidates per image and "
                                           f"class")
+    if case.startswith("rpn"):
+        stub = case.endswith("stub")
+        B = int(case[len("rpn"):len(case) - (4 if stub else 0)])
+        shapes = [(200, 336), (100, 168), (50, 84), (25, 42), (13, 21)]      # an 800 x 1344 image at strides 4 .. 64
+        m = nn.RegionProposal(256).evaluate().to(dev)
+        if stub:
+            from bigdl_amd.nn.abstractnn import AbstractModule
+
+            class SliceHead(AbstractModule):                   # objectness / regression are feature channels
+                def updateOutput(self, x):
+                    return Table(x[:, :3], x[:, 3:15])
+
+            m.head = SliceHead()
+            m.modules = [m.head]
+        feats = Table()
+        for i, (h, w) in enumerate(shapes):
+            f = torch.randn(B, 256, h, w, generator=g)
+            if stub:
+                f[:, 3:15] *= 0.3
+            feats[i + 1] = f.to(dev)
+        inp = T(feats, torch.tensor([800.0, 1344.0]))
+        anchors = sum(3 * h * w for h, w in shapes)
+        note = (f"RegionProposal(256) batch {B}, 5 levels 200x336 .. 13x21, {anchors} anchors per image, test mode "
+                f"1000 / 1000, nms 0.7" + (", head replaced by a channel-slicing stub" if stub else ""))
+        return (lambda: m.forward(inp)), note
     raise ValueError(f"unknown case {case!r}; known: {CASES}")
 
 
@@ -121,8 +149,9 @@ def tensors(out):
 
 
 def trace_child(case, path):
-    """Kernel names of a ``--one`` child under rocprofv3 --kernel-trace: a fresh process that builds the inputs and
-    runs the forward of ``path`` twice, so every per-forward count is half of what the trace holds."""
+    """(name, microseconds) of every kernel of a ``--one`` child under rocprofv3 --kernel-trace, in start order: a
+    fresh process that builds the inputs and runs the forward of ``path`` twice, so every per-forward count is half
+    of what the trace holds."""
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "det", "--",
                sys.executable, os.path.abspath(__file__), "--one", f"{case}:{path}"]
@@ -136,9 +165,10 @@ def trace_child(case, path):
         for f in files:
             with open(f, newline="") as fh:
                 for r in csv.DictReader(fh):
-                    rows.append((int(r["Start_Timestamp"]), r["Kernel_Name"]))
+                    rows.append((int(r["Start_Timestamp"]), r["Kernel_Name"],
+                                 (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
         rows.sort()
-        return [n for _, n in rows]
+        return [(n, us) for _, n, us in rows]
 
 
 def main():
@@ -189,13 +219,19 @@ def main():
             del run
             try:
                 for p, name in ((0, "loop"), (1, "batched")):
-                    names = trace_child(case, p)
-                    own = sum(1 for n in names if "nms_classes_kernel" in n or "roi_align_levels_fwd_kernel" in n)
+                    kernels = trace_child(case, p)
+                    names = [n for n, _ in kernels]
+                    own = sum(1 for n in names if any(k in n for k in OWN_KERNELS))
                     old = sum(1 for n in names if "nms_mask_kernel" in n or "nms_scan_kernel" in n
                               or "roi_align_fwd_kernel" in n)
                     say(f"  trace {name}: {len(names) // 2} launches per forward (input set-up included), of "
-                        f"them {own // 2} nms_classes / roi_align_levels and {old // 2} nms_mask / nms_scan "
-                        f"/ roi_align_fwd")
+                        f"them {own // 2} nms_classes / roi_align_levels / segmented_topk and {old // 2} nms_mask / "
+                        f"nms_scan / roi_align_fwd")
+                    for k in OWN_KERNELS[2:]:                  # one workgroup per segment: the longest one sets it
+                        us = [t for n, t in kernels if k in n]
+                        if us:
+                            say(f"    {k}: {len(us) // 2} per forward, last forward "
+                                + " ".join(f"{t:.1f}" for t in us[len(us) // 2:]) + " us")
             except (RuntimeError, OSError, KeyError, subprocess.TimeoutExpired) as e:
                 say(f"  kernel trace failed: {e}")
     text = "\n".join(lines)
