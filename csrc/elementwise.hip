@@ -135,8 +135,11 @@ __global__ void maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restr
     const int n = p / OH;
     float best[8];
     uint8_t bi[8];
+    // the winner starts at the first in-bounds tap (row-major), so a window whose in-bounds values are all -inf
+    // keeps a tap inside the image: tap 0 lies in the padding at a padded edge and the backward would drop dy
+    const uint8_t t0 = (uint8_t)(max(0, ph - oh * sh) * kw + max(0, pw - ow * sw));
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
+    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = t0; }
     for (int r = 0; r < kh; ++r) {
       const int ih = oh * sh - ph + r;
       if ((unsigned)ih >= (unsigned)H) continue;
@@ -245,8 +248,9 @@ __global__ __launch_bounds__(256) void maxpool_fwd_fixed_kernel(const bf16_t* __
       }
     float best[8];
     uint8_t bi[8];
+    const uint8_t t0 = (uint8_t)(max(0, -h0) * K + max(0, -w0));   // first in-bounds tap (see maxpool_fwd_kernel)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
+    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = t0; }
 #pragma unroll
     for (int t = 0; t < K * K; ++t) {
       if (!ok[t]) continue;
