@@ -808,6 +808,16 @@ void quantize_act(const Tensor& x, const Tensor& q, const Tensor& amax, const Te
                      (int)N, P, (int)C, (int)Cp, static_amax ? 1 : 0, stream());
 }
 
+// ConvArgs of an int8 call from conv_i8's 17-entry geo and taps: no bf16 epilogue operand, identity output rows. The
+// callers fill src / wt / out / bias.
+ConvArgs conv_i8_args(const std::vector<int64_t>& geo, const std::vector<int64_t>& taps, bool relu) {
+  ConvArgs a{};
+  conv_geometry(a, geo, taps);
+  a.ident_out = 1;
+  a.relu = relu ? 1 : 0;
+  return a;
+}
+
 // xscale: [N] per-sample scales, or None with xs_const (a static per-tensor scale); out bf16 / fp32 / int8 (int8:
 // requantized with out_scale). `out` may be a channel slice of a wider NHWC buffer (rows geo[10] = ldo apart).
 void conv_i8(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT& bias, const OptT& xscale,
@@ -821,29 +831,13 @@ void conv_i8(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
   TORCH_CHECK(mode != 2 || out_scale > 0, "conv_i8: int8 output needs out_scale > 0");
   TORCH_CHECK(out.is_cuda(), "conv_i8: out must be a device tensor");
   TORCH_CHECK(taps.size() % 3 == 0 && !taps.empty() && taps.size() / 3 <= CONV_MAX_TAPS, "conv_i8: bad taps");
-  ConvArgs a;
+  ConvArgs a = conv_i8_args(geo, taps, relu);
   a.src = reinterpret_cast<const uint16_t*>(src.data_ptr<int8_t>());
   a.wt = reinterpret_cast<const uint16_t*>(wt.data_ptr<int8_t>());
   a.out = reinterpret_cast<uint16_t*>(out.data_ptr());
-  a.bias = ocf(bias, "bias"); a.stats = nullptr; a.addend = nullptr; a.out32 = nullptr; a.accum32 = 0;
-  a.ws = nullptr; a.ksplit = 0; a.pstride = 0; a.pre = nullptr;
-  a.OW = a.OH = 0;
-  bigdl_conv_addend_stride(&a, 1, 1, 0, 0);
-  a.bnx = nullptr; a.bnz = nullptr; a.bnzm = nullptr; a.addzm = nullptr; a.bnmean = nullptr; a.bnaff = nullptr;
-  a.bnred = nullptr;
-  a.Nb = geo[0]; a.Hs = geo[1]; a.Ws = geo[2]; a.Cs = geo[3]; a.OH = geo[4]; a.OW = geo[5];
-  a.mul_h = geo[6]; a.mul_w = geo[7]; a.ldw = geo[8]; a.Ncol = geo[9]; a.ldo = geo[10];
-  a.OHo = geo[11]; a.OWo = geo[12]; a.omul_h = geo[13]; a.omul_w = geo[14]; a.ooff_h = geo[15]; a.ooff_w = geo[16];
-  a.ntaps = (int)(taps.size() / 3);
-  a.Kdim = a.ntaps * a.Cs;
-  a.M = a.Nb * a.OH * a.OW;
-  a.ident_out = 1;
-  a.relu = relu ? 1 : 0;
+  a.bias = ocf(bias, "bias");
   int max_tk = 0;
-  for (int t = 0; t < a.ntaps; ++t) {
-    a.tap_h[t] = (short)taps[3 * t]; a.tap_w[t] = (short)taps[3 * t + 1]; a.tap_k[t] = (short)taps[3 * t + 2];
-    max_tk = std::max(max_tk, (int)a.tap_k[t]);
-  }
+  for (int t = 0; t < a.ntaps; ++t) max_tk = std::max(max_tk, (int)a.tap_k[t]);
   TORCH_CHECK(src.numel() >= (int64_t)a.Nb * a.Hs * a.Ws * a.Cs, "conv_i8: src too small");
   TORCH_CHECK(wt.numel() >= (int64_t)(a.Ncol - 1) * a.ldw + (int64_t)(max_tk + 1) * a.Cs, "conv_i8: weight too small");
   const int64_t out_avail = (int64_t)(out.storage().nbytes() / out.element_size()) - out.storage_offset();
@@ -866,7 +860,27 @@ void conv_i8(const Tensor& src, const Tensor& wt, const Tensor& out, const OptT&
   const int rc = bigdl_conv_i8(&a, has_xs ? xscale->data_ptr<float>() : nullptr, (float)xs_const,
                                wscale.data_ptr<float>(), mode, mode == 2 ? (float)(1.0 / out_scale) : 0.f, add8,
                                (float)add_scale, add_ld, stream());
+  TORCH_CHECK(rc != I8_ERR_LAUNCH, "conv_i8: the chosen kernel refused the launch");
   TORCH_CHECK(rc == 0, "conv_i8: unsupported shape (channels must be a multiple of 16)");
+}
+
+// What conv_i8 would run for this geometry (conv_i8's geo / taps): (kernel name, BM, BN, stages, cpl, direct, fastk).
+// out_mode: 0 bf16, 1 fp32, 2 int8; flags: 1 = int8 addend, rows add_ld (default Ncol) apart; ldo_override replaces
+// geo[10] (a slice of a wider buffer). Operands are stood in for by an aligned non-null address: touches no GPU memory;
+// tests use it to check which kernel a case reaches.
+py::tuple conv_i8_plan_info(std::vector<int64_t> geo, std::vector<int64_t> taps, int64_t out_mode, int64_t flags,
+                            int64_t ldo_override, int64_t add_ld) {
+  TORCH_CHECK(geo.size() == 17 && taps.size() % 3 == 0 && !taps.empty() && taps.size() / 3 <= CONV_MAX_TAPS &&
+                  out_mode >= 0 && out_mode <= 2, "conv_i8_plan_info: bad geometry");
+  if (ldo_override > 0) geo[10] = ldo_override;
+  ConvArgs a = conv_i8_args(geo, taps, false);
+  uint16_t* present = reinterpret_cast<uint16_t*>(uintptr_t(256));
+  a.src = present; a.wt = present; a.out = present;
+  const I8Epi ep{nullptr, 1.f, reinterpret_cast<const float*>(present), (int)out_mode, out_mode == 2 ? 1.f : 0.f,
+                 (flags & 1) ? reinterpret_cast<const int8_t*>(present) : nullptr, 1.f,
+                 (long)(add_ld > 0 ? add_ld : a.Ncol)};
+  const I8Choice c = bigdl_conv_i8_choose(&a, &ep);
+  return py::make_tuple(bigdl_i8_kernel_name(c.kernel), c.BM, c.BN, c.stages, c.cpl, c.direct != 0, c.fastk != 0);
 }
 
 // int8 7x7/2 image stem straight from the fp32 NCHW image (conv_halo.hip stem_i8f_kernel): geo / taps are the width-
@@ -884,22 +898,10 @@ bool conv_i8_stem_f32(const Tensor& x, const Tensor& wt, const Tensor& out, cons
   TORCH_CHECK(mode != 0 || out.scalar_type() == at::kBFloat16, "conv_i8_stem_f32: out bf16, fp32 or int8");
   TORCH_CHECK(mode != 2 || out_scale > 0, "conv_i8_stem_f32: int8 output needs out_scale > 0");
   TORCH_CHECK(scale > 0 && wscale.numel() >= geo[9] && wscale.scalar_type() == at::kFloat, "conv_i8_stem_f32: scales");
-  ConvArgs a{};
-  a.src = nullptr;
+  ConvArgs a = conv_i8_args(geo, taps, relu);
   a.wt = reinterpret_cast<const uint16_t*>(wt.data_ptr<int8_t>());
   a.out = reinterpret_cast<uint16_t*>(out.data_ptr());
   a.bias = ocf(bias, "bias");
-  a.Nb = geo[0]; a.Hs = geo[1]; a.Ws = geo[2]; a.Cs = geo[3]; a.OH = geo[4]; a.OW = geo[5];
-  a.mul_h = geo[6]; a.mul_w = geo[7]; a.ldw = geo[8]; a.Ncol = geo[9]; a.ldo = geo[10];
-  a.OHo = geo[11]; a.OWo = geo[12]; a.omul_h = geo[13]; a.omul_w = geo[14]; a.ooff_h = geo[15]; a.ooff_w = geo[16];
-  a.ntaps = (int)(taps.size() / 3);
-  a.Kdim = a.ntaps * a.Cs;
-  a.M = a.Nb * a.OH * a.OW;
-  a.ident_out = 1;
-  a.relu = relu ? 1 : 0;
-  for (int t = 0; t < a.ntaps; ++t) {
-    a.tap_h[t] = (short)taps[3 * t]; a.tap_w[t] = (short)taps[3 * t + 1]; a.tap_k[t] = (short)taps[3 * t + 2];
-  }
   TORCH_CHECK(wt.numel() >= (int64_t)a.Ncol * a.ldw, "conv_i8_stem_f32: weight too small");
   const int64_t out_avail = (int64_t)(out.storage().nbytes() / out.element_size()) - out.storage_offset();
   TORCH_CHECK(a.ldo >= a.Ncol && out_avail >= (int64_t)(a.M - 1) * a.ldo + a.Ncol, "conv_i8_stem_f32: out too small");
@@ -2119,8 +2121,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_i8_s1", &bigdl_set_i8_s1);
   m.def("set_i8_epi", &bigdl_set_i8_epi);
   m.def("set_i8_shortk", &bigdl_set_i8_shortk);
-  m.def("get_i8_g3", &bigdl_get_i8_g3);
   m.def("set_i8_cpl", &bigdl_set_i8_cpl);
+  m.def("get_i8_g3", &bigdl_get_i8_g3);
+  m.def("get_i8_p8", &bigdl_get_i8_p8);
+  m.def("get_i8_s1", &bigdl_get_i8_s1);
+  m.def("get_i8_epi", &bigdl_get_i8_epi);
+  m.def("get_i8_shortk", &bigdl_get_i8_shortk);
   m.def("get_i8_cpl", &bigdl_get_i8_cpl);
+  m.def("conv_i8_plan_info", &conv_i8_plan_info, py::arg("geo"), py::arg("taps"), py::arg("out_mode") = 0,
+        py::arg("flags") = 0, py::arg("ldo_override") = 0, py::arg("add_ld") = 0,
+        "(kernel, BM, BN, stages, cpl, direct, fastk) conv_i8 would run; launches nothing");
   m.attr("arch") = "gfx950";
 }

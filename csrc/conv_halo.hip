@@ -795,6 +795,37 @@ void launch_halo_i8(const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
   conv_halo_kernel<W, RB, NIMG, KT, WPX, 3, 0, 1><<<dim3(nwg), dim3(256), 0, st>>>(a, ep);
 }
 
+// Geometry, extents and alignment the halo-tile kernels need, whatever BIGDL_CONV_HALO says (bigdl_conv_halo_applies
+// and bigdl_conv_halo_i8_applies add their switch and epilogue rules)
+int halo_geometry_ok(const ConvArgs* a) {
+  if (a->ntaps != 9 || a->mul_h != 1 || a->mul_w != 1 || !a->ident_out || a->out32 || a->pstride ||
+      a->Hs != a->OH || a->Ws != a->OW || a->Hs != a->Ws || a->Kdim != 9 * a->Cs || (a->Cs % 32) ||
+      (a->ldo % 8) || (a->Ncol % 8) || a->ldw < a->Kdim || (a->ldw % 8))
+    return 0;
+  const int W = a->Ws;
+  const int kt = W == 56 ? 64 : 128;
+  if (W != 56 && W != 28 && W != 14 && W != 7) return 0;
+  if (a->Ncol % kt) return 0;
+  unsigned seen = 0;
+  for (int t = 0; t < 9; ++t) {
+    if (a->tap_h[t] < -1 || a->tap_h[t] > 1 || a->tap_w[t] < -1 || a->tap_w[t] > 1 || a->tap_k[t] < 0 ||
+        a->tap_k[t] > 8)
+      return 0;
+    seen |= 1u << ((a->tap_h[t] + 1) * 3 + a->tap_w[t] + 1);
+  }
+  if (seen != 0x1ffu) return 0;
+  if ((size_t)a->Nb * a->Hs * a->Ws * a->Cs * 2 >= (1ull << 31) - (1ull << 20)) return 0;   // 32-bit buffer offsets
+  if ((size_t)a->Ncol * a->ldw * 2 >= (1ull << 31)) return 0;
+  // the epilogue reads / writes out, addend, bnx and the masks through the same 32-bit buffer offsets: the whole
+  // output extent (bf16 rows of ldo) must fit too (int8 callers go through here with the same bound)
+  const size_t M = (size_t)a->Nb * a->OH * a->OW;
+  if (((M - 1) * (size_t)a->ldo + a->Ncol) * 2 >= 0x7ff00000ull) return 0;
+  // a BN applied on load: the lean epilogue only (no addend / consumer-BN reduction), channel table in LDS
+  if (a->pre && (a->addend || (a->bnred && !a->stats) || a->Cs > PRE_MAXC)) return 0;
+  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  return al(a->src) && al(a->wt) && al(a->out) && al(a->addend) && al(a->bnx) && al(a->bnz);
+}
+
 }  // namespace
 
 extern "C" {
@@ -813,37 +844,13 @@ int bigdl_get_conv_halo() {
 
 // 1 when bigdl_conv_halo takes this forward / data-gradient GEMM (BIGDL_CONV_HALO=0 turns it off; 2 / 3: see below)
 int bigdl_conv_halo_applies(const ConvArgs* a) {
-  (void)bigdl_get_conv_halo();     // reads BIGDL_CONV_HALO once
-  if (!g_conv_halo || a->ntaps != 9 || a->mul_h != 1 || a->mul_w != 1 || !a->ident_out || a->out32 || a->pstride ||
-      a->Hs != a->OH || a->Ws != a->OW || a->Hs != a->Ws || a->Kdim != 9 * a->Cs || (a->Cs % 32) ||
-      (a->ldo % 8) || (a->Ncol % 8) || a->ldw < a->Kdim || (a->ldw % 8))
-    return 0;
-  const int W = a->Ws;
-  const int kt = W == 56 ? 64 : 128;
-  if (W != 56 && W != 28 && W != 14 && W != 7) return 0;
+  const int sw = bigdl_get_conv_halo();
+  if (!sw) return 0;
   // 2: only GEMMs with the lean epilogue (forwards); 3: also the full epilogue (data gradients) except at 56 x 56
   const bool lean = a->addend == nullptr && (a->bnred == nullptr || a->stats != nullptr);
-  if ((g_conv_halo == 2 && !lean) || (g_conv_halo == 3 && !lean && W == 56)) return 0;
-  if (a->Ncol % kt) return 0;
-  unsigned seen = 0;
-  for (int t = 0; t < 9; ++t) {
-    if (a->tap_h[t] < -1 || a->tap_h[t] > 1 || a->tap_w[t] < -1 || a->tap_w[t] > 1 || a->tap_k[t] < 0 ||
-        a->tap_k[t] > 8)
-      return 0;
-    seen |= 1u << ((a->tap_h[t] + 1) * 3 + a->tap_w[t] + 1);
-  }
-  if (seen != 0x1ffu) return 0;
-  if ((size_t)a->Nb * a->Hs * a->Ws * a->Cs * 2 >= (1ull << 31) - (1ull << 20)) return 0;   // 32-bit buffer offsets
-  if ((size_t)a->Ncol * a->ldw * 2 >= (1ull << 31)) return 0;
-  // the epilogue reads / writes out, addend, bnx and the masks through the same 32-bit buffer offsets: the whole
-  // output extent (bf16 rows of ldo) must fit too (int8 callers go through here with the same bound)
-  const size_t M = (size_t)a->Nb * a->OH * a->OW;
-  if (((M - 1) * (size_t)a->ldo + a->Ncol) * 2 >= 0x7ff00000ull) return 0;
-  // a BN applied on load: the lean epilogue only (no addend / consumer-BN reduction), channel table in LDS
-  if (a->pre && (a->addend || (a->bnred && !a->stats) || a->Cs > PRE_MAXC || (g_conv_halo != 1 && g_conv_halo != 2)))
-    return 0;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  return al(a->src) && al(a->wt) && al(a->out) && al(a->addend) && al(a->bnx) && al(a->bnz);
+  if ((sw == 2 && !lean) || (sw == 3 && !lean && a->Ws == 56)) return 0;
+  if (a->pre && sw != 1 && sw != 2) return 0;
+  return halo_geometry_ok(a);
 }
 
 int bigdl_conv_halo(const ConvArgs* a, hipStream_t st) {
@@ -904,16 +911,11 @@ int bigdl_dgrad_s2(const ConvArgs* a, hipStream_t st) {
 // output groups. BIGDL_CONV_HALO=0 turns it off too.
 int bigdl_conv_halo_i8_applies(const ConvArgs* a, const I8Epi* ep) {
   if (ep->add8 != nullptr || (a->Cs % 64) || (a->Ncol % 4) || (a->ldo % 4) || (a->ldw % 16)) return 0;
-  if (g_conv_halo < 0) (void)bigdl_conv_halo_applies(a);     // reads BIGDL_CONV_HALO once
-  if (!g_conv_halo) return 0;
-  // bigdl_conv_halo_applies's geometry checks, on int8 operands (16-byte aligned rows)
+  if (!bigdl_get_conv_halo()) return 0;
+  // the bf16 kernel's geometry checks, on int8 operands (16-byte aligned rows)
   ConvArgs b = *a;
   b.addend = nullptr; b.bnred = nullptr; b.stats = nullptr;
-  const int keep = g_conv_halo;
-  g_conv_halo = 1;
-  const int ok = bigdl_conv_halo_applies(&b);
-  g_conv_halo = keep;
-  return ok;
+  return halo_geometry_ok(&b);
 }
 
 // The int8 stem over the width im2col (see stem_i8_kernel): 7 row taps (r - 3) x 1, 32-byte rows, stride (2, 1),

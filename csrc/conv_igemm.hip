@@ -2837,8 +2837,10 @@ ConvSwitches& sw() {
   return s;
 }
 
-// compute units of the current device, read once
-int conv_cus() {
+}  // namespace
+
+// compute units of the current device, read once (shared with quant.hip through kernels.h)
+extern "C" int conv_cus() {
   static int cus = 0;
   if (cus == 0) {
     int dev = 0;
@@ -2848,6 +2850,8 @@ int conv_cus() {
   }
   return cus;
 }
+
+namespace {
 
 template <int BM, int BN, int WM>
 void launch_nt(const ConvArgs& a, bool fastk, hipStream_t st) {

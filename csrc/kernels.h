@@ -115,6 +115,28 @@ struct ConvChoice {
   long ws_floats;            // fp32 workspace the caller passes in ConvArgs::ws (0: none)
 };
 
+// The same for the int8 convolution (bigdl_conv_i8_choose). Ids <= 0 launch nothing: I8_NONE (no output rows) succeeds,
+// the negative ones are bigdl_conv_i8's error returns.
+enum I8Kernel {
+  I8_ERR_LAUNCH = -2,        // a launcher refused what its own predicate accepted
+  I8_ERR_SHAPE = -1,         // Cs % 16 != 0, or Kdim / ntaps out of range
+  I8_NONE = 0,
+  I8_STEM,                   // 7x7 / stride-2 image stem over its width im2col (conv_halo.hip stem_i8_kernel)
+  I8_HALO,                   // 3x3 from halo tiles (conv_halo.hip)
+  I8_S1,                     // streaming 1x1: cg 64-channel groups x 4 / cg pixel groups per workgroup
+  I8_P8,                     // 256 x 256 phase-interleaved
+  I8_G3,                     // multi-stage counted-vmcnt tile: BM x BN, `stages` deep (2 = the short-K form)
+  I8_GLDS,                   // 2-stage LDS-DMA tile: BM x BN
+};
+struct I8Choice {
+  int kernel;                // I8Kernel
+  int BM, BN;                // tile (0: stem / halo, whose tiles follow the image width)
+  int stages, cpl;           // g3: pipeline depth, channels per lane in the epilogue (0 elsewhere)
+  int direct;                // g3 / p8: register-direct epilogue
+  int fastk;                 // a K-step lies in one tap (g3: Cs % 64 == 0, glds: Cs % 128 == 0)
+  int cg;                    // s1: channel groups per workgroup (4, 2 or 1)
+};
+
 // The same for the weight gradient (bigdl_conv_wgrad_choose).
 enum WgradKernel {
   WGRAD_ERR_LAUNCH = -9,
@@ -175,6 +197,8 @@ void bigdl_colsum_bf16_ld(const uint16_t* x, float* out, long P, int K, long ld,
 // many floats in a->ws. CONV_ERR_PRE / CONV_ERR_ADDEND: no kernel that takes the GEMM applies a->pre / the subsampled
 // addend (the caller materialises the operand and chooses again).
 ConvChoice bigdl_conv_nt_choose(const ConvArgs* a);
+// compute units of the current device, read once (conv_igemm.hip)
+int conv_cus();
 const char* bigdl_conv_kernel_name(int kernel);
 // Subsampled addend (ConvArgs::add_sh): bigdl_conv_addend_stride sets the stride, the addend's pixel geometry and the
 // reciprocals (sh = sw = 1 switches it off); bigdl_conv_addend_stride_applies is 1 when bigdl_conv_nt_choose accepts
@@ -328,8 +352,13 @@ int bigdl_quantize_act(const void* x, int is_bf16, int8_t* q, float* amax, float
 // xscale: [N] per-sample activation scales or nullptr (xs_const for the whole tensor); out_mode 0 bf16, 1 fp32,
 // 2 int8 requantized with out_inv = 1 / out_scale. Output rows are a->ldo elements apart.
 // add8 (optional): int8 residual addend [M][add_ld] with scale add_scale, summed before the ReLU.
+// Launches what bigdl_conv_i8_choose chose; 0 on success, else a negative I8Kernel code.
 int bigdl_conv_i8(const ConvArgs* a, const float* xscale, float xs_const, const float* wscale, int out_mode,
                   float out_inv, const int8_t* add8, float add_scale, long add_ld, hipStream_t st);
+// Kernel choice for an int8 call: a pure host function of the args and the BIGDL_I8_* / BIGDL_STEM_I8 /
+// BIGDL_CONV_HALO switches. It launches nothing, queries no device and tests pointers for null / alignment only.
+I8Choice bigdl_conv_i8_choose(const ConvArgs* a, const I8Epi* ep);
+const char* bigdl_i8_kernel_name(int kernel);
 // int8 NHWC pooling (max or average, same scale in and out; output rows ldo apart), graph-input quantizer
 // (fp32 NCHW -> int8 NHWC, static scale), bf16 rows -> int8 rows at a channel offset, int8 rows -> bf16.
 void bigdl_pool_i8(const int8_t* x, int8_t* y, int N, int H, int W, int Cp, int OH, int OW, int kh, int kw, int sh,
@@ -377,7 +406,6 @@ int bigdl_wgrad_halo_plan(WgradArgs* a);
 // 1 when bigdl_conv_wgrad applies a->pre on load (the halo kernel takes the GEMM), else the caller materialises src
 int bigdl_wgrad_pre_applies(const WgradArgs* a);
 int bigdl_wgrad_halo(const WgradArgs* a, hipStream_t st);
-void bigdl_set_i8_s1(int v);
 int bigdl_get_conv_impl();
 void bigdl_set_conv_g4(int v);
 void bigdl_set_conv_shortk(int v);
@@ -389,12 +417,18 @@ void bigdl_set_wgrad_g3(int v);
 int bigdl_get_wgrad_g3();
 void bigdl_set_wgrad_tr_asm(int v);
 int bigdl_get_wgrad_tr_asm();
+// the BIGDL_I8_* switches (quant.hip I8Switches)
 void bigdl_set_i8_g3(int v);
 void bigdl_set_i8_p8(int v);
+void bigdl_set_i8_s1(int v);
 void bigdl_set_i8_epi(int v);
 void bigdl_set_i8_shortk(int v);
-int bigdl_get_i8_g3();
 void bigdl_set_i8_cpl(int v);
+int bigdl_get_i8_g3();
+int bigdl_get_i8_p8();
+int bigdl_get_i8_s1();
+int bigdl_get_i8_epi();
+int bigdl_get_i8_shortk();
 int bigdl_get_i8_cpl();
 
 // Input pipeline: crop + flip + channel reorder + normalise of a uint8 [N, H, W, 3] BGR batch.

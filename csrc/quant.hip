@@ -450,7 +450,7 @@ __device__ __forceinline__ void i8_tile_epilogue(const ConvArgs& a, const I8Epi&
 // channels of one pixel per 16 x 16 tile, so each tile is finished in registers and stored as one 4-byte int8 group
 // (8-byte bf16 / 16-byte fp32) per lane — no LDS round trip, no barrier — with the per-channel factors folded once:
 // q = rn(acc * (xs * wsc * out_inv) + bias * out_inv + add * add_scale * out_inv). Needs Ncol % 4 == 0 and
-// ldo % 4 == 0 (4-byte aligned groups); the caller checks (i8_direct_ok).
+// ldo % 4 == 0 (4-byte aligned groups); the chooser checks (i8_direct_operands_ok).
 template <int MI, int NI>
 __device__ __forceinline__ void i8_tile_epilogue_direct(const ConvArgs& a, const I8Epi& ep, v4i (&acc)[MI][NI],
                                                         int mbase, int nbase, int lane) {
@@ -1029,40 +1029,51 @@ __global__ void dequantize_rows_kernel(const int8_t* __restrict__ q, bf16_t* __r
 }  // namespace
 
 namespace {
-// BIGDL_I8_CPL (default 16): channels per lane in the int8 3-stage kernel's epilogue (16 = 16-byte int8 stores)
-int g_i8_cpl = -1;
-int i8_cpl() {
-  if (g_i8_cpl < 0) {
-    const char* e = getenv("BIGDL_I8_CPL");
-    g_i8_cpl = e ? atoi(e) : 16;   // 16: ResNet-50 int8 4.19 -> 3.90 ms (profiles/r3_int8_epilogue_ab.txt)
-  }
-  return g_i8_cpl;
+// Dispatch. Every int8 switch lives in one table (I8Switches); bigdl_conv_i8_choose is the only place that decides
+// which kernel runs, and bigdl_conv_i8 only launches what it chose. (BIGDL_STEM_I8 and BIGDL_CONV_HALO belong to
+// conv_halo.hip's predicates.)
+struct I8Switches {
+  // BIGDL_I8_G3 (default 1): the 3-stage counted-vmcnt 128 x 128 int8 kernel for Ncol > 64, Cs % 64 == 0.
+  // 2: also the 256 x 128 tile (2 x 2 waves of 128 x 64: 32 i8 MFMAs per wave between barriers instead of 16, 2
+  // workgroups per CU) when its grid still fills two workgroups per CU; 3: the 256 x 128 tile always (tests).
+  int g3;
+  // BIGDL_I8_P8 (default 1): the 256 x 256 phase-interleaved int8 kernel for Cs % 128 == 0, Kdim >= 1024, Ncol >= 256
+  // and >= 160 tiles (the bf16 kernel's rule); 2: whenever the shape allows (tests); 0: off
+  int p8;
+  // BIGDL_I8_S1 (default 1): the streaming 1x1 int8 kernel wherever it applies
+  int s1;
+  // BIGDL_I8_EPI (default 0): 1 = register-direct int8 epilogue where the output groups are 4-byte aligned. Measured
+  // slower: ResNet-50 int8 3.83 -> 5.11 ms (4-byte groups scattered over 16 pixel rows per store instruction vs the
+  // LDS-staged 16-byte rows; profiles/r4_int8_epilogue_direct_ab.txt)
+  int epi;
+  // BIGDL_I8_SHORTK (default 0): 1 = the two-stage, 4-workgroups-per-CU 128 x 128 variant when Kdim <= 128 (fast-K);
+  // 2: that variant with the 8-channel epilogue (106 VGPRs, no spill, vs 16 spilled VGPRs with 16 channels per lane).
+  // Measured: 1 slower (ResNet-50 int8 3.83 -> 4.22 ms), 2 neutral (3.85 ms) — the one-K-step layers are not
+  // occupancy-bound (profiles/r4_shortk_ab.txt)
+  int shortk;
+  // BIGDL_I8_CPL (default 16): channels per lane in the int8 3-stage kernel's epilogue (16 = 16-byte int8 stores).
+  // 16: ResNet-50 int8 4.19 -> 3.90 ms (profiles/r3_int8_epilogue_ab.txt)
+  int cpl;
+};
+
+I8Switches& i8sw() {
+  static I8Switches s = [] {
+    auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    I8Switches t;
+    t.g3 = env("BIGDL_I8_G3", 1);
+    t.p8 = env("BIGDL_I8_P8", 1);
+    t.s1 = env("BIGDL_I8_S1", 1);
+    t.epi = env("BIGDL_I8_EPI", 0);
+    t.shortk = env("BIGDL_I8_SHORTK", 0);
+    t.cpl = env("BIGDL_I8_CPL", 16);
+    return t;
+  }();
+  return s;
 }
 
-// BIGDL_I8_EPI (default 0): 1 = register-direct int8 epilogue where the output groups are 4-byte aligned. Measured
-// slower: ResNet-50 int8 3.83 -> 5.11 ms (4-byte groups scattered over 16 pixel rows per store instruction vs the
-// LDS-staged 16-byte rows; profiles/r4_int8_epilogue_direct_ab.txt)
-int g_i8_epi = -1;
-bool i8_direct_ok(const ConvArgs& a, const I8Epi& ep) {
-  if (g_i8_epi < 0) {
-    const char* e = getenv("BIGDL_I8_EPI");
-    g_i8_epi = e ? atoi(e) : 0;
-  }
-  return g_i8_epi != 0 && a.Ncol % 4 == 0 && a.ldo % 4 == 0 && (ep.add8 == nullptr || ep.add_ld % 4 == 0) &&
-         (ep.out_mode != 1 || a.ldo % 4 == 0);
-}
-
-// BIGDL_I8_SHORTK (default 0): 1 = the two-stage, 4-workgroups-per-CU 128 x 128 variant when Kdim <= 128 (fast-K);
-// 2: that variant with the 8-channel epilogue (106 VGPRs, no spill, vs 16 spilled VGPRs with 16 channels per lane).
-// Measured: 1 slower (ResNet-50 int8 3.83 -> 4.22 ms), 2 neutral (3.85 ms) — the one-K-step layers are not
-// occupancy-bound (profiles/r4_shortk_ab.txt)
-int g_i8_shortk = -1;
-bool i8_shortk() {
-  if (g_i8_shortk < 0) {
-    const char* e = getenv("BIGDL_I8_SHORTK");
-    g_i8_shortk = e ? atoi(e) : 0;
-  }
-  return g_i8_shortk != 0;
+// operands of the register-direct int8 epilogue (I8Switches::epi): 4-byte aligned output / addend groups
+bool i8_direct_operands_ok(const ConvArgs& a, const I8Epi& ep) {
+  return a.Ncol % 4 == 0 && a.ldo % 4 == 0 && (ep.add8 == nullptr || ep.add_ld % 4 == 0);
 }
 
 // Streaming 1x1 int8 kernel: the structure of conv_nt_s1_kernel (conv_igemm.hip) on v_mfma_i32_16x16x64_i8 for the
@@ -1231,13 +1242,9 @@ __global__ __launch_bounds__(256, 2) void conv_i8_s1_kernel(ConvArgs a, I8Epi ep
   }
 }
 
-int g_i8_s1 = -1;   // BIGDL_I8_S1 (default 1): the streaming 1x1 int8 kernel wherever it applies
-bool i8_s1_applies(const ConvArgs& a, const I8Epi& ep) {
-  if (g_i8_s1 < 0) {
-    const char* e = getenv("BIGDL_I8_S1");
-    g_i8_s1 = e ? atoi(e) : 1;
-  }
-  if (!g_i8_s1 || !a.ident_out || a.ntaps != 1 || a.tap_h[0] || a.tap_w[0] || a.tap_k[0]) return false;
+// operands of conv_i8_s1_kernel (I8Switches::s1)
+bool i8_s1_operands_ok(const ConvArgs& a, const I8Epi& ep) {
+  if (!a.ident_out || a.ntaps != 1 || a.tap_h[0] || a.tap_w[0] || a.tap_k[0]) return false;
   if (a.mul_h != 1 || a.mul_w != 1 || a.Hs != a.OH || a.Ws != a.OW) return false;
   if ((a.Kdim != 64 && a.Kdim != 128 && a.Kdim != 256) || a.Cs != a.Kdim || (a.Ncol % 64) || (a.ldw % 16)) return false;
   const int osz = ep.out_mode == 2 ? 1 : ep.out_mode == 1 ? 4 : 2;
@@ -1248,18 +1255,13 @@ bool i8_s1_applies(const ConvArgs& a, const I8Epi& ep) {
   return al(a.src) && al(a.wt) && al(a.out) && al(ep.add8);
 }
 
-template <int K, int CG, int BMW, int OUT>
+// I8_S1: the instantiation for (Kdim, channel groups, output mode, addend); persistent grid of two workgroups per CU
+template <int K, int CG, int OUT>
 void launch_i8_s1_o(const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
+  constexpr int BMW = K == 256 ? 16 : 32;
   const int nchb = a.Ncol / (64 * CG);
   const int tiles = (a.M + BMW * (4 / CG) - 1) / (BMW * (4 / CG));
-  int per = std::max(1, (2 * cus) / nchb);
+  int per = std::max(1, (2 * conv_cus()) / nchb);
   per = std::min(per, tiles);
   if (ep.add8) conv_i8_s1_kernel<K, CG, BMW, OUT, true><<<dim3(per * nchb), dim3(256), 0, st>>>(a, ep);
   else conv_i8_s1_kernel<K, CG, BMW, OUT, false><<<dim3(per * nchb), dim3(256), 0, st>>>(a, ep);
@@ -1267,44 +1269,41 @@ void launch_i8_s1_o(const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
 
 template <int K, int CG>
 void launch_i8_s1_cg(const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
-  constexpr int BW = K == 256 ? 16 : 32;
-  if (ep.out_mode == 2) launch_i8_s1_o<K, CG, BW, 2>(a, ep, st);
-  else if (ep.out_mode == 1) launch_i8_s1_o<K, CG, BW, 1>(a, ep, st);
-  else launch_i8_s1_o<K, CG, BW, 0>(a, ep, st);
+  if (ep.out_mode == 2) launch_i8_s1_o<K, CG, 2>(a, ep, st);
+  else if (ep.out_mode == 1) launch_i8_s1_o<K, CG, 1>(a, ep, st);
+  else launch_i8_s1_o<K, CG, 0>(a, ep, st);
 }
 
-void launch_i8_s1(const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
-  const int cg = (a.Ncol % 256 == 0) ? 4 : (a.Ncol % 128 == 0) ? 2 : 1;
-#define I8S1_K(KK)                                 \
-  if (cg == 4) launch_i8_s1_cg<KK, 4>(a, ep, st);   \
-  else if (cg == 2) launch_i8_s1_cg<KK, 2>(a, ep, st); \
-  else launch_i8_s1_cg<KK, 1>(a, ep, st);
-  if (a.Kdim == 64) { I8S1_K(64) }
-  else if (a.Kdim == 128) { I8S1_K(128) }
-  else { I8S1_K(256) }
-#undef I8S1_K
+template <int K>
+void launch_i8_s1(const I8Choice& c, const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
+  if (c.cg == 4) launch_i8_s1_cg<K, 4>(a, ep, st);
+  else if (c.cg == 2) launch_i8_s1_cg<K, 2>(a, ep, st);
+  else launch_i8_s1_cg<K, 1>(a, ep, st);
 }
 
+// I8_G3 on a BM x BN tile: the instantiation for the choice's (stages, cpl, direct, fastk)
 template <int BM, int BN, int WGM, int WGN>
-void launch_i8_g3(int g, bool fk, const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
+void launch_i8_g3(const I8Choice& c, const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
+  const int g = ((a.M + BM - 1) / BM) * ((a.Ncol + BN - 1) / BN);
   if constexpr (BM == 128 && BN == 128) {
-    if (fk && a.Kdim <= 128 && i8_shortk() && !i8_direct_ok(a, ep)) {
-      if (i8_cpl() == 16 && g_i8_shortk != 2) conv_i8_g3_kernel<BM, BN, WGM, WGN, true, 16, false, 2><<<g, 256, 0, st>>>(a, ep);
+    if (c.stages == 2) {
+      if (c.cpl == 16) conv_i8_g3_kernel<BM, BN, WGM, WGN, true, 16, false, 2><<<g, 256, 0, st>>>(a, ep);
       else conv_i8_g3_kernel<BM, BN, WGM, WGN, true, 8, false, 2><<<g, 256, 0, st>>>(a, ep);
       return;
     }
   }
-  if (fk && i8_direct_ok(a, ep)) {
-    conv_i8_g3_kernel<BM, BN, WGM, WGN, true, 16, true><<<g, 256, 0, st>>>(a, ep);
-    return;
-  }
-  if (i8_cpl() == 16 && BN / WGN >= 16) {
-    if (fk) conv_i8_g3_kernel<BM, BN, WGM, WGN, true, 16><<<g, 256, 0, st>>>(a, ep);
-    else conv_i8_g3_kernel<BM, BN, WGM, WGN, false, 16><<<g, 256, 0, st>>>(a, ep);
-  } else {
-    if (fk) conv_i8_g3_kernel<BM, BN, WGM, WGN, true, 8><<<g, 256, 0, st>>>(a, ep);
-    else conv_i8_g3_kernel<BM, BN, WGM, WGN, false, 8><<<g, 256, 0, st>>>(a, ep);
-  }
+  if (c.direct) conv_i8_g3_kernel<BM, BN, WGM, WGN, true, 16, true><<<g, 256, 0, st>>>(a, ep);
+  else if (c.cpl == 16 && c.fastk) conv_i8_g3_kernel<BM, BN, WGM, WGN, true, 16><<<g, 256, 0, st>>>(a, ep);
+  else if (c.cpl == 16) conv_i8_g3_kernel<BM, BN, WGM, WGN, false, 16><<<g, 256, 0, st>>>(a, ep);
+  else if (c.fastk) conv_i8_g3_kernel<BM, BN, WGM, WGN, true, 8><<<g, 256, 0, st>>>(a, ep);
+  else conv_i8_g3_kernel<BM, BN, WGM, WGN, false, 8><<<g, 256, 0, st>>>(a, ep);
+}
+
+template <int BM, int BN, int WM>
+void launch_i8_glds(const I8Choice& c, const ConvArgs& a, const I8Epi& ep, hipStream_t st) {
+  const int g = ((a.M + BM - 1) / BM) * ((a.Ncol + BN - 1) / BN);
+  if (c.fastk) conv_i8_glds_kernel<BM, BN, WM, true><<<g, 256, 0, st>>>(a, ep);
+  else conv_i8_glds_kernel<BM, BN, WM, false><<<g, 256, 0, st>>>(a, ep);
 }
 
 }  // namespace
@@ -1336,77 +1335,102 @@ int bigdl_quantize_act(const void* x, int is_bf16, int8_t* q, float* amax, float
   return 0;
 }
 
-int g_i8_g3 = -1;
-// BIGDL_I8_G3 (default 1): the 3-stage counted-vmcnt 128 x 128 int8 kernel for Ncol > 64, Cs % 64 == 0.
-// 2: also the 256 x 128 tile (2 x 2 waves of 128 x 64: 32 i8 MFMAs per wave between barriers instead of 16, 2
-// workgroups per CU) when its grid still fills two workgroups per CU; 3: the 256 x 128 tile always (tests).
-static bool i8_g3() {
-  if (g_i8_g3 < 0) {
-    const char* e = getenv("BIGDL_I8_G3");
-    g_i8_g3 = e ? atoi(e) : 1;
-  }
-  return g_i8_g3 != 0;
-}
-void bigdl_set_i8_g3(int v) { g_i8_g3 = v; }
-// BIGDL_I8_P8 (default 1): the 256 x 256 phase-interleaved int8 kernel for Cs % 128 == 0, Kdim >= 1024, Ncol >= 256
-// and >= 160 tiles (the bf16 kernel's rule); 2: whenever the shape allows (tests); 0: off
-int g_i8_p8 = -1;
-static bool i8_p8() {
-  if (g_i8_p8 < 0) {
-    const char* e = getenv("BIGDL_I8_P8");
-    g_i8_p8 = e ? atoi(e) : 1;
-  }
-  return g_i8_p8 != 0;
-}
-void bigdl_set_i8_p8(int v) { g_i8_p8 = v; }
-void bigdl_set_i8_s1(int v) { g_i8_s1 = v; }
-void bigdl_set_i8_epi(int v) { g_i8_epi = v; }
-void bigdl_set_i8_shortk(int v) { g_i8_shortk = v; }
-void bigdl_set_i8_cpl(int v) { g_i8_cpl = v; }
-int bigdl_get_i8_cpl() { return i8_cpl(); }
-int bigdl_get_i8_g3() { return i8_g3() ? g_i8_g3 : 0; }
+void bigdl_set_i8_g3(int v) { i8sw().g3 = v; }
+void bigdl_set_i8_p8(int v) { i8sw().p8 = v; }
+void bigdl_set_i8_s1(int v) { i8sw().s1 = v; }
+void bigdl_set_i8_epi(int v) { i8sw().epi = v; }
+void bigdl_set_i8_shortk(int v) { i8sw().shortk = v; }
+void bigdl_set_i8_cpl(int v) { i8sw().cpl = v; }
+int bigdl_get_i8_g3() { return i8sw().g3; }
+int bigdl_get_i8_p8() { return i8sw().p8; }
+int bigdl_get_i8_s1() { return i8sw().s1; }
+int bigdl_get_i8_epi() { return i8sw().epi; }
+int bigdl_get_i8_shortk() { return i8sw().shortk; }
+int bigdl_get_i8_cpl() { return i8sw().cpl; }
 
+const char* bigdl_i8_kernel_name(int kernel) {
+  switch (kernel) {
+    case I8_NONE: return "none";
+    case I8_STEM: return "stem";
+    case I8_HALO: return "halo";
+    case I8_S1: return "s1";
+    case I8_P8: return "p8";
+    case I8_G3: return "g3";
+    case I8_GLDS: return "glds";
+    default: return "refused";
+  }
+}
+
+// The ladder: first kernel that takes the GEMM, in order of preference. I8Choice{kernel, BM, BN, stages, cpl, direct,
+// fastk, cg}
+I8Choice bigdl_conv_i8_choose(const ConvArgs* a, const I8Epi* ep) {
+  const I8Switches& s = i8sw();
+  if (a->Cs % 16 != 0 || a->Kdim != a->ntaps * a->Cs || a->ntaps < 1 || a->ntaps > CONV_MAX_TAPS)
+    return I8Choice{I8_ERR_SHAPE};
+  if (a->M <= 0) return I8Choice{I8_NONE};
+  const bool fk = a->Cs % QBK == 0, g3fk = a->Cs % 64 == 0;
+  const bool direct = s.epi != 0 && i8_direct_operands_ok(*a, *ep);
+  // the 7x7/2 image stem over its width im2col: staged-row kernel (conv_halo.hip stem_i8_kernel)
+  if (bigdl_stem_i8_applies(a, ep)) return I8Choice{I8_STEM};
+  // 3x3 / stride-1 / pad-1: the halo-tile kernel on the i8 matrix cores (conv_halo.hip)
+  if (bigdl_conv_halo_i8_applies(a, ep)) return I8Choice{I8_HALO};
+  if (s.s1 && i8_s1_operands_ok(*a, *ep)) {
+    // a workgroup's waves: cg 64-channel groups x 4 / cg pixel groups of 16 (Kdim 256) or 32 pixels
+    const int cg = (a->Ncol % 256 == 0) ? 4 : (a->Ncol % 128 == 0) ? 2 : 1;
+    return I8Choice{I8_S1, (a->Kdim == 256 ? 16 : 32) * (4 / cg), 64 * cg, 0, 0, 0, 1, cg};
+  }
+  const long p8_tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
+  if (s.p8 && fk && a->Kdim >= 1024 && a->Ncol >= 256 && a->Ncol % 16 == 0 && (s.p8 == 2 || p8_tiles >= 160))
+    return I8Choice{I8_P8, 256, 256, 0, 0, direct, 1};
+  // the tile kernels: four waves stacked along M for narrow outputs, else 128 x 128 (or I8Switches::g3's 256 x 128)
+  const int g3_256 = ((a->M + 255) / 256) * ((a->Ncol + 127) / 128);
+  const bool tall = a->Ncol <= 64 || s.g3 == 3 || (s.g3 == 2 && g3_256 >= 512);
+  const int BM = tall ? 256 : 128, BN = a->Ncol <= 32 ? 32 : a->Ncol <= 64 ? 64 : 128;
+  if (!s.g3) return I8Choice{I8_GLDS, BM, BN, 0, 0, 0, fk};
+  const int cpl = s.cpl == 16 ? 16 : 8;
+  if (BM == 128 && g3fk && a->Kdim <= 128 && s.shortk && !direct)
+    return I8Choice{I8_G3, BM, BN, 2, s.shortk == 2 ? 8 : cpl, 0, 1};
+  if (g3fk && direct) return I8Choice{I8_G3, BM, BN, 3, 16, 1, 1};
+  return I8Choice{I8_G3, BM, BN, 3, cpl, 0, g3fk};
+}
+
+// Launches what bigdl_conv_i8_choose chose for `a`. Returns 0 on success, else the choice's negative I8Kernel code
+// or I8_ERR_LAUNCH.
 int bigdl_conv_i8(const ConvArgs* a, const float* xscale, float xs_const, const float* wscale, int out_mode,
                   float out_inv, const int8_t* add8, float add_scale, long add_ld, hipStream_t st) {
-  if (a->Cs % 16 != 0 || a->Kdim != a->ntaps * a->Cs || a->ntaps < 1 || a->ntaps > CONV_MAX_TAPS) return -1;
-  if (a->M <= 0) return 0;
-  const int nwg = ((a->M + 127) / 128) * ((a->Ncol + 127) / 128);
   const I8Epi ep{xscale, xs_const, wscale, out_mode, out_inv, add8, add_scale, add_ld};
-  const bool fk = a->Cs % QBK == 0;
-  const bool g3fk = a->Cs % 64 == 0;
-  const long p8_tiles = (long)((a->M + 255) / 256) * ((a->Ncol + 255) / 256);
-  if (bigdl_stem_i8_applies(a, &ep) && bigdl_stem_i8(a, &ep, st) == 0) {
-    // the 7x7/2 image stem over its width im2col: staged-row kernel (conv_halo.hip stem_i8_kernel)
-  } else if (bigdl_conv_halo_i8_applies(a, &ep) && bigdl_conv_halo_i8(a, &ep, st) == 0) {
-    // 3x3 / stride-1 / pad-1: the halo-tile kernel on the i8 matrix cores (conv_halo.hip)
-  } else if (i8_s1_applies(*a, ep)) {
-    launch_i8_s1(*a, ep, st);
-  } else if (i8_p8() && fk && a->Kdim >= 1024 && a->Ncol >= 256 && a->Ncol % 16 == 0 &&
-      (g_i8_p8 == 2 || p8_tiles >= 160)) {
-    if (i8_direct_ok(*a, ep)) conv_i8_p8_kernel<true><<<dim3((unsigned)p8_tiles), dim3(512), 0, st>>>(*a, ep);
-    else conv_i8_p8_kernel<false><<<dim3((unsigned)p8_tiles), dim3(512), 0, st>>>(*a, ep);
-  } else if (a->Ncol <= 64 && i8_g3()) {
-    const int bn = a->Ncol <= 32 ? 32 : 64;
-    const int g = ((a->M + 255) / 256) * ((a->Ncol + bn - 1) / bn);
-    if (bn == 32) launch_i8_g3<256, 32, 4, 1>(g, g3fk, *a, ep, st);
-    else launch_i8_g3<256, 64, 4, 1>(g, g3fk, *a, ep, st);
-  } else if (a->Ncol <= 32) {
-    const int g = ((a->M + 255) / 256) * ((a->Ncol + 31) / 32);
-    if (fk) conv_i8_glds_kernel<256, 32, 4, true><<<g, 256, 0, st>>>(*a, ep);
-    else conv_i8_glds_kernel<256, 32, 4, false><<<g, 256, 0, st>>>(*a, ep);
-  } else if (a->Ncol <= 64) {
-    const int g = ((a->M + 255) / 256) * ((a->Ncol + 63) / 64);
-    if (fk) conv_i8_glds_kernel<256, 64, 4, true><<<g, 256, 0, st>>>(*a, ep);
-    else conv_i8_glds_kernel<256, 64, 4, false><<<g, 256, 0, st>>>(*a, ep);
-  } else if (i8_g3() && (g_i8_g3 == 3 || (g_i8_g3 == 2 && ((a->M + 255) / 256) * ((a->Ncol + 127) / 128) >= 512))) {
-    const int g = ((a->M + 255) / 256) * ((a->Ncol + 127) / 128);
-    launch_i8_g3<256, 128, 2, 2>(g, g3fk, *a, ep, st);
-  } else if (i8_g3()) {
-    launch_i8_g3<128, 128, 2, 2>(nwg, g3fk, *a, ep, st);
-  } else if (fk) {
-    conv_i8_glds_kernel<128, 128, 2, true><<<nwg, 256, 0, st>>>(*a, ep);
-  } else {
-    conv_i8_glds_kernel<128, 128, 2, false><<<nwg, 256, 0, st>>>(*a, ep);
+  const I8Choice c = bigdl_conv_i8_choose(a, &ep);
+  if (c.kernel <= 0) return c.kernel;
+  switch (c.kernel) {
+    case I8_STEM:
+      if (bigdl_stem_i8(a, &ep, st) != 0) return I8_ERR_LAUNCH;
+      break;
+    case I8_HALO:
+      if (bigdl_conv_halo_i8(a, &ep, st) != 0) return I8_ERR_LAUNCH;
+      break;
+    case I8_S1:
+      if (a->Kdim == 64) launch_i8_s1<64>(c, *a, ep, st);
+      else if (a->Kdim == 128) launch_i8_s1<128>(c, *a, ep, st);
+      else launch_i8_s1<256>(c, *a, ep, st);
+      break;
+    case I8_P8: {
+      const dim3 grid((unsigned)(((a->M + 255) / 256) * (long)((a->Ncol + 255) / 256)));
+      if (c.direct) conv_i8_p8_kernel<true><<<grid, dim3(512), 0, st>>>(*a, ep);
+      else conv_i8_p8_kernel<false><<<grid, dim3(512), 0, st>>>(*a, ep);
+      break;
+    }
+    case I8_G3:
+      if (c.BN == 32) launch_i8_g3<256, 32, 4, 1>(c, *a, ep, st);
+      else if (c.BN == 64) launch_i8_g3<256, 64, 4, 1>(c, *a, ep, st);
+      else if (c.BM == 256) launch_i8_g3<256, 128, 2, 2>(c, *a, ep, st);
+      else launch_i8_g3<128, 128, 2, 2>(c, *a, ep, st);
+      break;
+    case I8_GLDS:
+      if (c.BN == 32) launch_i8_glds<256, 32, 4>(c, *a, ep, st);
+      else if (c.BN == 64) launch_i8_glds<256, 64, 4>(c, *a, ep, st);
+      else launch_i8_glds<128, 128, 2>(c, *a, ep, st);
+      break;
+    default: return I8_ERR_LAUNCH;
   }
   HIP_LAUNCH_CHECK();
   return 0;

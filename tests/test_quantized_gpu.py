@@ -1,4 +1,6 @@
 """Int8 HIP kernels (csrc/quant.hip) vs exact integer / CPU-emulated references (GPU only)."""
+import contextlib
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -28,6 +30,54 @@ def test_quantize_act_matches_reference(dtype):
     assert torch.allclose(s.cpu(), sr)
 
 
+I8_SWITCHES = ("g3", "p8", "s1", "epi", "shortk", "cpl")
+I8_DEFAULTS = dict(g3=1, p8=1, s1=1, epi=0, shortk=0, cpl=16)
+
+
+@contextlib.contextmanager
+def _i8_switches(**want):
+    """The BIGDL_I8_* switches at their defaults except for `want` inside the block; afterwards all six are back at
+    what the getters returned before (whatever the environment had asked for)."""
+    C_ = native.get()
+    found = {k: getattr(C_, "get_i8_" + k)() for k in I8_SWITCHES}
+    try:
+        for k in I8_SWITCHES:
+            getattr(C_, "set_i8_" + k)(want.get(k, I8_DEFAULTS[k]))
+        yield C_
+    finally:
+        for k, v in found.items():
+            getattr(C_, "set_i8_" + k)(v)
+
+
+def _geo(case):
+    from bigdl_amd.ops.conv import _fwd_taps, out_size
+
+    N, C, H, W, K, R, S, st, pd, dl = case
+    OH, OW = out_size(H, R, st, pd, dl), out_size(W, S, st, pd, dl)
+    return [N, H, W, C, OH, OW, st, st, R * S * C, K, K, OH, OW, 1, 1, 0, 0], _fwd_taps(R, S, pd, pd, dl, dl)
+
+
+def _reaches(case, want, out_mode=1, addend=False):
+    """conv_i8 on `case` (dense output of out_mode 0 bf16 / 1 fp32 / 2 int8, with or without the int8 addend) runs
+    `want` = (kernel, BM, BN, stages, cpl, direct, fastk) under the switches in force; launches nothing."""
+    geo, taps = _geo(case)
+    got = tuple(native.get().conv_i8_plan_info(geo, taps, out_mode, 1 if addend else 0))
+    assert got == want, (case, got, want)
+
+
+def _tile_kernel(case, g3=1, cpl=16, epi=0):
+    """What the tile kernels' rules give for a case none of stem / halo / s1 / p8 takes: the 256 x 32 / 256 x 64 tiles
+    for Ncol <= 32 / 64, else 128 x 128 (256 x 128 with g3 = 3); g3 = 0 is the 2-stage kernel (fast-K: Cs % 128 == 0),
+    else the 3-stage one (fast-K: Cs % 64 == 0) with `cpl` channels per lane, register-direct under epi on fast-K
+    layers whose output groups are 4-byte aligned."""
+    C, K = case[1], case[4]
+    BM, BN = (256, 32) if K <= 32 else (256, 64) if K <= 64 else (256, 128) if g3 == 3 else (128, 128)
+    if g3 == 0:
+        return ("glds", BM, BN, 0, 0, False, C % 128 == 0)
+    direct = bool(epi) and C % 64 == 0 and K % 4 == 0
+    return ("g3", BM, BN, 3, 16 if direct else cpl, direct, C % 64 == 0)
+
+
 # N, C, H, W, K, R, S, stride, pad, dil
 I8_CASES = [
     (2, 16, 9, 9, 24, 3, 3, 1, 1, 1),
@@ -41,6 +91,8 @@ I8_CASES = [
     (2, 64, 12, 12, 64, 3, 3, 1, 1, 1),     # narrow 256 x 64 tile
     (3, 128, 9, 9, 24, 1, 1, 1, 0, 1),      # narrow 256 x 32 tile (Ncol tail)
     (2, 64, 15, 15, 40, 3, 3, 2, 1, 1),     # 256 x 64, stride 2, Ncol tail
+    (2, 48, 9, 9, 72, 3, 3, 1, 1, 1),       # per-lane taps (Cs % 64 != 0) on the 128 x 128 / 256 x 128 tiles
+    (2, 128, 8, 8, 48, 1, 1, 1, 0, 1),      # 256 x 64 tile with Cs % 128 == 0 (the 2-stage kernel's fast-K form)
 ]
 
 
@@ -52,23 +104,18 @@ def test_conv_i8_exact_integer(case, g3, cpl):
     3-stage counted-vmcnt kernel (BIGDL_I8_G3, 128 x 128 tiles, Cs % 64 == 0; 3 = its 256 x 128 tile) and the 2-stage one."""
     from bigdl_amd.ops.conv import _fwd_taps, out_size
 
-    C_ = native.get()
-    old, old_cpl = C_.get_i8_g3(), C_.get_i8_cpl()
-    C_.set_i8_g3(g3)
-    C_.set_i8_cpl(cpl)     # channels per lane in the 3-stage kernel's LDS-staged epilogue (16: 16-byte stores)
-    C_.set_i8_epi(1 if cpl == 16 else 0)   # cpl 16: the register-direct epilogue (BIGDL_I8_EPI=1) where it applies
-    try:
-        _conv_i8_exact(case)
-    finally:
-        C_.set_i8_g3(old)
-        C_.set_i8_cpl(old_cpl)
-        C_.set_i8_epi(0)
+    # cpl 16: with the register-direct epilogue (BIGDL_I8_EPI=1) where it applies; cpl: channels per lane in the
+    # 3-stage kernel's LDS-staged epilogue (16: 16-byte stores)
+    epi = 1 if cpl == 16 else 0
+    with _i8_switches(g3=g3, cpl=cpl, epi=epi):
+        _conv_i8_exact(case, _tile_kernel(case, g3, cpl, epi))
 
 
 I8_SHORTK_CASES = [
     (3, 64, 14, 14, 200, 1, 1, 1, 0, 1),    # one K-step, Ncol tail
     (3, 128, 13, 13, 256, 1, 1, 1, 0, 1),   # two K-steps, M tail
     (2, 64, 15, 15, 136, 1, 1, 2, 0, 1),    # stride 2, Ncol tail
+    (3, 128, 13, 13, 136, 1, 1, 1, 0, 1),   # two K-steps, M tail, Ncol tail (not the streaming kernel's: Ncol % 64 != 0)
 ]
 
 
@@ -77,12 +124,13 @@ I8_SHORTK_CASES = [
 def test_conv_i8_shortk_exact_integer(case, mode):
     """Two-stage 128 x 128 short-K int8 kernel (Kdim <= 128; BIGDL_I8_SHORTK 1: 16 channels per lane in the epilogue,
     2: 8; off by default): fp32 output equal to the integer conv."""
-    C_ = native.get()
-    C_.set_i8_shortk(mode)
-    try:
-        _conv_i8_exact(case)
-    finally:
-        C_.set_i8_shortk(0)
+    want = ("g3", 128, 128, 2, 16 if mode == 1 else 8, False, True)
+    if case == I8_SHORTK_CASES[1]:
+        # Cs = Kdim = 128 with Ncol % 64 == 0 and identity pixels: the streaming 1x1 kernel (BIGDL_I8_S1, default 1)
+        # sits above the tile kernels and takes this one; I8_SHORTK_CASES[3] is its two-K-step shape with an Ncol tail
+        want = ("s1", 32, 256, 0, 0, False, True)
+    with _i8_switches(shortk=mode):
+        _conv_i8_exact(case, want)
 
 
 I8_P8_CASES = [
@@ -90,6 +138,7 @@ I8_P8_CASES = [
     (3, 1024, 7, 7, 512, 1, 1, 1, 0, 1),    # 1x1, two N tiles, M tail
     (2, 128, 14, 14, 272, 3, 3, 2, 1, 1),   # stride 2, Ncol tail (272)
     (5, 512, 7, 7, 2048, 1, 1, 1, 0, 1),    # 8 N tiles
+    (2, 1024, 7, 7, 2048, 1, 1, 1, 0, 1),   # 8 N tiles with Kdim >= 1024
 ]
 
 
@@ -97,12 +146,19 @@ I8_P8_CASES = [
 def test_conv_i8_p8_exact_integer(case):
     """256 x 256 phase-interleaved int8 kernel (BIGDL_I8_P8=2 forces it wherever Cs % 128 == 0, Kdim >= 1024,
     Ncol >= 256): fp32 output equal to the integer conv."""
-    C_ = native.get()
-    C_.set_i8_p8(2)
-    try:
-        _conv_i8_exact(case)
-    finally:
-        C_.set_i8_p8(1)
+    want = ("p8", 256, 256, 0, 0, False, True)
+    if case == I8_P8_CASES[3]:
+        # Kdim = 512 is below the kernel's Kdim >= 1024: the 3-stage 128 x 128 kernel takes it (I8_P8_CASES[4] is the
+        # same output width at Kdim 1024)
+        want = ("g3", 128, 128, 3, 16, False, True)
+    with _i8_switches(p8=2):
+        _conv_i8_exact(case, want)
+
+
+def test_conv_i8_p8_direct_epilogue_exact_integer():
+    """The 256 x 256 kernel's register-direct epilogue (BIGDL_I8_EPI=1, 4-byte aligned output groups)."""
+    with _i8_switches(p8=2, epi=1):
+        _conv_i8_exact(I8_P8_CASES[0], ("p8", 256, 256, 0, 0, True, True))
 
 
 @pytest.mark.parametrize("relu", [False, True])
@@ -113,11 +169,12 @@ def test_conv_i8_int8_output_exact(case, g3, relu):
     conv + bias + addend, clamped to [-127, 127] (or [0, 127] with the ReLU) — exact, for every int8 kernel."""
     from bigdl_amd.ops.conv import _fwd_taps, out_size
 
-    C_ = native.get()
-    old = C_.get_i8_g3()
-    C_.set_i8_g3(g3)
-    C_.set_i8_p8(2 if g3 == 3 else 1)   # g3 == 3: the 256 x 256 kernel wherever the shape allows
-    try:
+    p8 = 2 if g3 == 3 else 1            # g3 == 3: the 256 x 256 kernel wherever the shape allows
+    want = _tile_kernel(case, g3)
+    if p8 == 2 and case == I8_P8_CASES[1]:
+        want = ("p8", 256, 256, 0, 0, False, True)
+    with _i8_switches(g3=g3, p8=p8) as C_:
+        _reaches(case, want, out_mode=2, addend=True)
         N, C, H, W, K, R, S, st, pd, dl = case
         g = torch.Generator().manual_seed(3)
         x = torch.randint(-3, 4, (N, H, W, C), generator=g, dtype=torch.int8)   # small: most outputs inside the range
@@ -135,14 +192,13 @@ def test_conv_i8_int8_output_exact(case, g3, relu):
                    1.0, 1.0, add.view(N, OH, OW, K).cuda(), 1.0)
         torch.cuda.synchronize()
         assert torch.equal(out.cpu(), exp)
-    finally:
-        C_.set_i8_g3(old)
-        C_.set_i8_p8(1)
 
 
-def _conv_i8_exact(case):
+def _conv_i8_exact(case, want):
+    """fp32 output (unit scales) equal to the integer conv + bias, on the kernel `want` (see _reaches)."""
     from bigdl_amd.ops.conv import _fwd_taps, out_size
 
+    _reaches(case, want)
     N, C, H, W, K, R, S, st, pd, dl = case
     g = torch.Generator().manual_seed(1)
     x = torch.randint(-127, 128, (N, H, W, C), generator=g, dtype=torch.int8)
@@ -210,6 +266,9 @@ I8_S1_CASES = [
     (4, 256, 9, 9, 64, 1, 1, 1, 0, 1),      # K 256 (4 i8 MFMA K-steps), one channel group
     (5, 64, 11, 11, 128, 1, 1, 1, 0, 1),    # two channel groups
     (2, 256, 7, 7, 192, 1, 1, 1, 0, 1),     # three one-group channel blocks
+    (2, 64, 7, 7, 64, 1, 1, 1, 0, 1),       # K 64, one channel group (four 32-pixel groups)
+    (2, 256, 7, 7, 256, 1, 1, 1, 0, 1),     # K 256, four channel groups
+    (2, 256, 7, 7, 128, 1, 1, 1, 0, 1),     # K 256, two channel groups
 ]
 
 
@@ -220,8 +279,12 @@ def test_conv_i8_s1_exact(case):
     from bigdl_amd.ops.conv import _fwd_taps, out_size
 
     C_ = native.get()
-    _conv_i8_exact(case)
     N, C, H, W, K, R, S, st, pd, dl = case
+    # a workgroup's four waves: cg 64-channel groups x 4 / cg pixel groups of 32 (K 256: 16) pixels
+    cg = 4 if K % 256 == 0 else 2 if K % 128 == 0 else 1
+    want = {1: ("s1", (16 if C == 256 else 32) * (4 // cg), 64 * cg, 0, 0, False, True), 0: _tile_kernel(case)}
+    with _i8_switches():
+        _conv_i8_exact(case, want[1])
     g = torch.Generator().manual_seed(3)
     x = torch.randint(-3, 4, (N, H, W, C), generator=g, dtype=torch.int8)
     w = torch.randint(-3, 4, (K, R, S, C), generator=g, dtype=torch.int8)
@@ -233,8 +296,9 @@ def test_conv_i8_s1_exact(case):
     geo = [N, H, W, C, OH, OW, st, st, R * S * C, K, K, OH, OW, 1, 1, 0, 0]
     outs = {}
     for s1 in (1, 0):
-        C_.set_i8_s1(s1)
-        try:
+        with _i8_switches(s1=s1):
+            _reaches(case, want[s1], out_mode=2, addend=True)
+            _reaches(case, want[s1], out_mode=0)
             for relu in (False, True):
                 out = torch.zeros(N * OH * OW, K, dtype=torch.int8, device="cuda")
                 C_.conv_i8(x.cuda(), w.cuda(), out, bias.cuda(), torch.ones(N, device="cuda"),
@@ -246,8 +310,6 @@ def test_conv_i8_s1_exact(case):
                            _fwd_taps(R, S, pd, pd, dl, dl), relu)
                 torch.cuda.synchronize()
                 outs[(s1, relu)] = (out.cpu(), bf.float().cpu(), xs.cpu())
-        finally:
-            C_.set_i8_s1(1)
     for relu in (False, True):
         exp = (ref + bias.double() + add.double()).clamp(0 if relu else -127, 127).to(torch.int8)
         assert torch.equal(outs[(1, relu)][0], exp)
@@ -276,7 +338,9 @@ def test_conv_i8_halo_exact(case):
     from bigdl_amd.ops.conv import _fwd_taps, out_size
 
     C_ = native.get()
-    _conv_i8_exact(case)
+    want = {1: ("halo", 0, 0, 0, 0, False, False), 0: _tile_kernel(case)}
+    with _i8_switches():
+        _conv_i8_exact(case, want[1])
     N, C, H, W, K, R, S, st, pd, dl = case
     g = torch.Generator().manual_seed(7)
     x = torch.randint(-4, 5, (N, H, W, C), generator=g, dtype=torch.int8)
@@ -290,10 +354,12 @@ def test_conv_i8_halo_exact(case):
     for halo in (1, 0):
         C_.set_conv_halo(halo)
         try:
-            out = torch.zeros(N * OH * OW, K, dtype=torch.int8, device="cuda")
-            C_.conv_i8(x.cuda(), w.cuda(), out, bias.cuda(), torch.ones(N, device="cuda"),
-                       torch.ones(K, device="cuda"), geo, _fwd_taps(R, S, pd, pd, dl, dl), True, 1.0, 1.0)
-            torch.cuda.synchronize()
+            with _i8_switches():
+                _reaches(case, want[halo], out_mode=2)
+                out = torch.zeros(N * OH * OW, K, dtype=torch.int8, device="cuda")
+                C_.conv_i8(x.cuda(), w.cuda(), out, bias.cuda(), torch.ones(N, device="cuda"),
+                           torch.ones(K, device="cuda"), geo, _fwd_taps(R, S, pd, pd, dl, dl), True, 1.0, 1.0)
+                torch.cuda.synchronize()
             outs[halo] = out.cpu()
         finally:
             C_.set_conv_halo(1)
@@ -327,10 +393,15 @@ def test_stem_i8_kernel_exact(N, H, relu, mode):
     for on in (1, 0):
         C_.set_stem_i8(on)
         try:
-            out = torch.zeros(N * OH * OW, K, dtype=dt, device="cuda")
-            C_.conv_i8(q, wp.cuda(), out, bias.cuda(), None, torch.ones(K, device="cuda"), geo,
-                       _fwd_taps(7, 1, 3, 0, 1, 1), relu, 1.0, 1.0 if mode == "i8" else 0.0, None, 0.0)
-            torch.cuda.synchronize()
+            # off: Ncol = 64 with Cs = 32, the 3-stage kernel's 256 x 64 tile with per-lane taps
+            want = ("stem", 0, 0, 0, 0, False, False) if on else ("g3", 256, 64, 3, 16, False, False)
+            with _i8_switches():
+                got = tuple(C_.conv_i8_plan_info(geo, _fwd_taps(7, 1, 3, 0, 1, 1), {"bf16": 0, "f32": 1, "i8": 2}[mode]))
+                assert got == want, got
+                out = torch.zeros(N * OH * OW, K, dtype=dt, device="cuda")
+                C_.conv_i8(q, wp.cuda(), out, bias.cuda(), None, torch.ones(K, device="cuda"), geo,
+                           _fwd_taps(7, 1, 3, 0, 1, 1), relu, 1.0, 1.0 if mode == "i8" else 0.0, None, 0.0)
+                torch.cuda.synchronize()
             outs[on] = out.cpu()
         finally:
             C_.set_stem_i8(1)
