@@ -40,7 +40,24 @@ def is_gpu(t):
     return isinstance(t, torch.Tensor) and t.is_cuda
 
 
+def _densify(t):
+    """The flat kernels read numel() consecutive elements (the bindings refuse anything else): a view with gaps or
+    overlap is copied; a dense tensor of any dimension order (contiguous, channels-last, channels-last-3d, a
+    transpose) passes as it is and the result keeps its layout."""
+    return t if t.is_contiguous() or torch.ops.aten.is_non_overlapping_and_dense(t) else t.contiguous()
+
+
+def _like(t, ref):
+    """``t`` in the element order of the dense tensor ``ref`` (same shape)."""
+    if t.stride() == ref.stride():
+        return t
+    if ref.is_contiguous() or (ref.dim() == 4 and ref.is_contiguous(memory_format=CL)):
+        return t.contiguous(memory_format=_fmt(ref))
+    return torch.empty_like(ref, dtype=t.dtype).copy_(t)      # empty_like keeps the strides of a dense tensor
+
+
 def relu_gpu(x, out=None):
+    x = _densify(x)
     if out is None:
         out = torch.empty_like(x)
     native.get().relu_fwd(x, out)
@@ -48,18 +65,19 @@ def relu_gpu(x, out=None):
 
 
 def relu_bwd_gpu(dy, y, out=None):
+    y = _densify(y)
     if out is None:
         out = torch.empty_like(y)
     if dy.dtype != BF16:
         dy = dy.to(BF16)
-    dy = dy.contiguous(memory_format=_fmt(y))
+    dy = _like(dy, y)
     native.get().relu_bwd(dy, y, out)
     return out
 
 
 def add_gpu(a, b, out=None):
-    if b.stride() != a.stride():
-        b = b.contiguous(memory_format=_fmt(a))
+    a = _densify(a)
+    b = _like(b, a)
     if out is None:
         out = torch.empty_like(a)
     native.get().add_bf16(a, b, out)

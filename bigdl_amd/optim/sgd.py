@@ -230,13 +230,15 @@ class EpochDecayWithWarmUp(LearningRateSchedule):
 
 
 def segment_decay_vector(seg, n, base, device):
-    """Expand (segment starts, decays) into a per-element decay vector (CPU / fallback path)."""
+    """Expand (segment starts, decays) into a per-element decay vector (CPU / fallback path). As in the kernels'
+    ``seg_decay`` (csrc/elementwise.hip) the first segment also covers any element below its start;
+    ``fold_regularizers`` always starts the first segment at 0, so no such element exists in a training step."""
     off = seg[0].to("cpu").tolist()
     val = seg[1].to("cpu").tolist()
     v = torch.zeros(n, device=device)
     for i, (o, d) in enumerate(zip(off, val)):
         end = off[i + 1] if i + 1 < len(off) else base + n
-        a, b = max(o - base, 0), min(end - base, n)
+        a, b = (max(o - base, 0) if i else 0), min(end - base, n)
         if b > a and d != 0:
             v[a:b] = d
     return v

@@ -429,16 +429,33 @@ void spin_us(double us, const Tensor& done) {
   TORCH_CHECK(done.is_cuda() && done.scalar_type() == at::kInt && done.numel() >= 1, "spin_us: done must be int32 cuda");
   bigdl_spin_us(us, done.data_ptr<int>(), stream());
 }
+// The flat element-wise kernels read their tensors as one run of numel() elements: every tensor must be dense, and two
+// tensors must enumerate their elements in the same order (equal strides on every dimension longer than 1, e.g. both
+// channels-last; tensors of different shapes must both be contiguous). A strided view would be read as if flat.
+void same_flat_order(const Tensor& a, const Tensor& b, const char* what) {
+  TORCH_CHECK(a.is_non_overlapping_and_dense() && b.is_non_overlapping_and_dense(), what, ": tensors must be dense");
+  if (a.sizes() == b.sizes()) {
+    for (int64_t d = 0; d < a.dim(); ++d)
+      TORCH_CHECK(a.size(d) <= 1 || a.stride(d) == b.stride(d), what, ": tensors must share one memory layout");
+  } else {
+    TORCH_CHECK(a.is_contiguous() && b.is_contiguous(), what, ": tensors of different shapes must be contiguous");
+  }
+}
 void relu_fwd(const Tensor& x, const Tensor& y) {
   TORCH_CHECK(x.numel() == y.numel(), "relu: size");
+  same_flat_order(x, y, "relu");
   bigdl_relu_fwd(cbf(x, "x"), mbf(y, "y"), x.numel(), stream());
 }
 void relu_bwd(const Tensor& dy, const Tensor& y, const Tensor& dx) {
   TORCH_CHECK(dy.numel() == y.numel() && dx.numel() == y.numel(), "relu_bwd: size");
+  same_flat_order(dy, y, "relu_bwd");
+  same_flat_order(dx, y, "relu_bwd");
   bigdl_relu_bwd(cbf(dy, "dy"), cbf(y, "y"), mbf(dx, "dx"), y.numel(), stream());
 }
 void add_bf16(const Tensor& a, const Tensor& b, const Tensor& y) {
   TORCH_CHECK(a.numel() == b.numel() && a.numel() == y.numel(), "add: size");
+  same_flat_order(a, b, "add");
+  same_flat_order(y, a, "add");
   bigdl_add_bf16(cbf(a, "a"), cbf(b, "b"), mbf(y, "y"), a.numel(), stream());
 }
 void nchw_to_nhwc(const Tensor& x, const Tensor& y, int64_t Cp) {
@@ -744,6 +761,8 @@ void sgd_step(const Tensor& w, const Tensor& g, const OptT& mom, const OptT& w16
               double momentum, double dampening, bool nesterov, bool first, const OptT& lr_dev,
               const OptT& seg_off, const OptT& seg_wd, int64_t base) {
   TORCH_CHECK(w.numel() == g.numel(), "sgd: size");
+  TORCH_CHECK(w.is_contiguous() && g.is_contiguous() && (!(mom && mom->defined()) || mom->is_contiguous()) &&
+                  (!(w16 && w16->defined()) || w16->is_contiguous()), "sgd: w, g, mom and w16 must be contiguous");
   TORCH_CHECK(!(mom && mom->defined()) || mom->numel() == w.numel(), "sgd: mom has ", mom ? mom->numel() : 0,
               " elements, w has ", w.numel());
   TORCH_CHECK(!(w16 && w16->defined()) || w16->numel() == w.numel(), "sgd: w16 size");
@@ -754,32 +773,42 @@ void sgd_step(const Tensor& w, const Tensor& g, const OptT& mom, const OptT& w16
     so = (const long*)seg_off->data_ptr();
     nseg = (int)seg_off->numel();
     TORCH_CHECK(seg_wd && seg_wd->numel() == nseg, "sgd: seg_wd size");
+    TORCH_CHECK(seg_off->is_contiguous() && seg_wd->is_contiguous(), "sgd: seg_off / seg_wd must be contiguous");
   }
   bigdl_sgd_step(mf(w, "w"), cf(g, "g"), omf(mom, "mom"), ombf(w16, "w16"), w.numel(), ocf(lr_dev, "lr_dev"),
-                 (float)lr, (float)wd, (float)momentum, (float)dampening, nesterov ? 1 : 0, first ? 1 : 0, so,
+                 (float)lr, (float)wd, (float)momentum, dampening, nesterov ? 1 : 0, first ? 1 : 0, so,
                  ocf(seg_wd, "seg_wd"), nseg, (long)base, stream());
 }
 void adam_step(const Tensor& w, const Tensor& g, const Tensor& m, const Tensor& v, const OptT& w16, double lr,
                double b1, double b2, double eps, double wd, double bc1, double bc2) {
   TORCH_CHECK(w.numel() == g.numel() && m.numel() == w.numel() && v.numel() == w.numel(), "adam: state size");
-  bigdl_adam_step(mf(w, "w"), cf(g, "g"), mf(m, "m"), mf(v, "v"), ombf(w16, "w16"), w.numel(), (float)lr, (float)b1,
-                  (float)b2, (float)eps, (float)wd, (float)bc1, (float)bc2, stream());
+  TORCH_CHECK(!(w16 && w16->defined()) || (w16->numel() == w.numel() && w16->is_contiguous()), "adam: w16");
+  TORCH_CHECK(w.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(),
+              "adam: w, g, m and v must be contiguous");
+  bigdl_adam_step(mf(w, "w"), cf(g, "g"), mf(m, "m"), mf(v, "v"), ombf(w16, "w16"), w.numel(), (float)lr, b1,
+                  b2, (float)eps, (float)wd, (float)bc1, (float)bc2, stream());
 }
 void optim_step(int64_t method, const Tensor& x, const Tensor& g, const Tensor& s1, const OptT& s2, const OptT& w16,
                 double a, double b, double c, double d, double e) {
   TORCH_CHECK(g.numel() == x.numel() && s1.numel() == x.numel() && (!s2 || !s2->defined() || s2->numel() == x.numel())
                   && (!w16 || !w16->defined() || w16->numel() >= x.numel()), "optim_step: buffer sizes");
   for (const Tensor* t : {&x, &g, &s1}) TORCH_CHECK(t->is_contiguous(), "optim_step: contiguous buffers");
-  const OptimHP hp{(float)a, (float)b, (float)c, (float)d, (float)e};
+  const double rate = method == 2 ? a : b;      // the moving-average decay of RMSprop / Adadelta / Adamax
+  const OptimHP hp{(float)a, (float)b, (float)c, (float)d, (float)e, (float)(1.0 - rate)};
   TORCH_CHECK(bigdl_optim_step((int)method, &hp, mf(x, "x"), cf(g, "g"), mf(s1, "s1"), omf(s2, "s2"),
                                ombf(w16, "w16"), x.numel(), stream()) == 0, "optim_step: unknown method");
 }
-void sumsq(const Tensor& x, const Tensor& out) {
+// workspace = false: deterministic mode without its slot workspace (the one-block form of bigdl_sumsq, which the C
+// entry point keeps for callers without an allocator). No caller in bigdl_amd/ passes it: the argument exists so that
+// tests/test_step_tail_edges_gpu.py can reach that form.
+void sumsq(const Tensor& x, const Tensor& out, bool workspace) {
+  TORCH_CHECK(x.is_non_overlapping_and_dense() && out.numel() >= 1, "sumsq: x must be dense, out one float");
   Tensor ws;      // deterministic mode: per-call slot workspace (re-entrant across streams)
-  if (bigdl_deterministic()) ws = at::empty({BIGDL_DET_SLOTS}, out.options().dtype(at::kFloat));
+  if (bigdl_deterministic() && workspace) ws = at::empty({BIGDL_DET_SLOTS}, out.options().dtype(at::kFloat));
   bigdl_sumsq(cf(x, "x"), mf(out, "out"), x.numel(), stream(), ws.defined() ? ws.data_ptr<float>() : nullptr);
 }
 void scale_f32(const Tensor& x, const OptT& sdev, double s) {
+  TORCH_CHECK(x.is_non_overlapping_and_dense(), "scale_f32: x must be dense");
   bigdl_scale_f32(mf(x, "x"), x.numel(), ocf(sdev, "scale"), (float)s, stream());
 }
 void lstm_cell_fwd(const Tensor& gates, const OptT& c_prev, const Tensor& c, const Tensor& h, const Tensor& act) {
@@ -1935,6 +1964,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("res_shift") = py::none());
   m.def("bn_slot_reduce", &bn_slot_reduce);
   m.attr("STAT_SLOTS") = BIGDL_STAT_SLOTS;
+  m.attr("DET_SLOTS") = BIGDL_DET_SLOTS;
+  m.attr("XENT_SLOTS") = BIGDL_XENT_SLOTS;
   m.def("bn_bwd_reduce", &bn_bwd_reduce, py::arg("dz"), py::arg("z"), py::arg("x"), py::arg("mean"), py::arg("red"),
         py::arg("P"), py::arg("C"), py::arg("aff") = py::none(), py::arg("zm") = py::none());
   m.def("bn_bwd_apply", &bn_bwd_apply, py::arg("dz"), py::arg("z"), py::arg("x"), py::arg("mean"), py::arg("invstd"),
@@ -1985,7 +2016,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sgd_step", &sgd_step, py::arg("w"), py::arg("g"), py::arg("mom"), py::arg("w16"), py::arg("lr"), py::arg("wd"), py::arg("momentum"), py::arg("dampening"), py::arg("nesterov"), py::arg("first"), py::arg("lr_dev") = py::none(), py::arg("seg_off") = py::none(), py::arg("seg_wd") = py::none(), py::arg("base") = 0);
   m.def("adam_step", &adam_step);
   m.def("optim_step", &optim_step);
-  m.def("sumsq", &sumsq);
+  m.def("sumsq", &sumsq, py::arg("x"), py::arg("out"), py::arg("workspace") = true);
   m.def("scale_f32", &scale_f32);
   m.def("lstm_cell_fwd", &lstm_cell_fwd);
   m.def("lstm_cell_bwd", &lstm_cell_bwd);

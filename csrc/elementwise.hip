@@ -20,13 +20,23 @@ inline int grid_cap(long work, int cap = 8192) {
   return (int)g;
 }
 
+// the 16-byte kernels need every pointer on a 16-byte boundary; a view at an odd element offset takes the scalar
+// kernel over the whole range (as bigdl_sgd_step / bigdl_optim_step choose)
+inline bool aligned16(const void* a, const void* b, const void* c = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
+
 #define GRID_STRIDE(i, n) for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
 __global__ void relu_fwd_kernel(const v4u* __restrict__ x, v4u* __restrict__ y, long n8) {
   GRID_STRIDE(i, n8) {
     v4u v = x[i], o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack2bf(fmaxf(lo_bf(v[e]), 0.f), fmaxf(hi_bf(v[e]), 0.f));
+    for (int e = 0; e < 4; ++e) {   // x <= 0 ? +0 : x on the bits: a NaN passes with its payload (Threshold.scala:83)
+      const unsigned lo = lo_bf(v[e]) <= 0.f ? 0u : (v[e] & 0xffffu);
+      const unsigned hi = hi_bf(v[e]) <= 0.f ? 0u : (v[e] & 0xffff0000u);
+      o[e] = lo | hi;
+    }
     y[i] = o;
   }
 }
@@ -52,9 +62,9 @@ __global__ void add_kernel(const v4u* __restrict__ a, const v4u* __restrict__ b,
     y[i] = o;
   }
 }
-// tail-safe scalar versions for n % 8 != 0
+// scalar versions: the n % 8 tail (from s), or the whole range (s = 0) when a pointer is not 16-byte aligned
 __global__ void relu_fwd_tail(const bf16_t* x, bf16_t* y, long s, long n) {
-  GRID_STRIDE(i, n - s) y[s + i] = f2bf(fmaxf(bf2f(x[s + i]), 0.f));
+  GRID_STRIDE(i, n - s) y[s + i] = bf2f(x[s + i]) <= 0.f ? (bf16_t)0 : x[s + i];
 }
 __global__ void relu_bwd_tail(const bf16_t* dy, const bf16_t* y, bf16_t* dx, long s, long n) {
   GRID_STRIDE(i, n - s) dx[s + i] = bf2f(y[s + i]) > 0.f ? dy[s + i] : (bf16_t)0;
@@ -109,13 +119,18 @@ __global__ void __launch_bounds__(256) colsum_bf16_kernel(const bf16_t* __restri
   }
 }
 
-__global__ void cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, long n) {
-  const long n4 = n >> 2;
+// elements [h, h + 4 n4) go as 16-byte loads / 8-byte stores (the host picks the head h <= 3 that aligns x + h and
+// y + h, or h = n: all scalar); the head and the tail are scalar
+__global__ void cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, long n, long h) {
+  const long n4 = (n - h) >> 2;
   GRID_STRIDE(i, n4) {
-    const v4f v = reinterpret_cast<const v4f*>(x)[i];
-    reinterpret_cast<v2u*>(y)[i] = v2u{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+    const v4f v = reinterpret_cast<const v4f*>(x + h)[i];
+    reinterpret_cast<v2u*>(y + h)[i] = v2u{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
   }
-  GRID_STRIDE(j, n - n4 * 4) y[n4 * 4 + j] = f2bf(x[n4 * 4 + j]);
+  GRID_STRIDE(j, n - n4 * 4) {
+    const long k = j < h ? j : n4 * 4 + j;
+    y[k] = f2bf(x[k]);
+  }
 }
 __global__ void cast_bf16_f32_kernel(const bf16_t* __restrict__ x, float* __restrict__ y, long n) {
   GRID_STRIDE(i, n) y[i] = bf2f(x[i]);
@@ -544,7 +559,7 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void softmax_xent_kernel(const bf16_t* __restrict__ lb, const float* __restrict__ lf,
                                                            const float* __restrict__ labels, float* __restrict__ loss,
                                                            bf16_t* __restrict__ db, float* __restrict__ df, int B, int K,
-                                                           float label_base, float grad_scale,
+                                                           float label_base, float gscale,
                                                            float* __restrict__ loss_slots) {
   __shared__ float part[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -553,7 +568,8 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const bf16_t* __restr
     const long base = (long)row * K;
     float mx = -INFINITY, se = 0.f;
     auto acc = [&](float v) {
-      if (v > mx) { se = se * __expf(mx - v) + 1.f; mx = v; } else { se += __expf(v - mx); }
+      // a -inf element adds 0 and never forms -inf - -inf (mx is still -inf when a lane's stride starts with one)
+      if (v > mx) { se = se * __expf(mx - v) + 1.f; mx = v; } else if (v != -INFINITY) { se += __expf(v - mx); }
     };
     if (VEC && lb) {            // 8 bf16 per lane per load
       const v4u* p = (const v4u*)(lb + base);
@@ -576,12 +592,13 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const bf16_t* __restr
     const float s_all = wave_sum(se);
     const float lse = m_all + __logf(s_all);
     const int tgt = (int)(labels[row] - label_base);
-    if (lane == 0) {
-      const float xt = (tgt >= 0 && tgt < K) ? (lb ? bf2f(lb[base + tgt]) : lf[base + tgt]) : lse;
-      my_loss += (lse - xt) * grad_scale;
-    }
+    // a label outside [0, K) is a skipped sample (ClassNLLCriterion.scala:134, :206 paddingValue): nothing joins the
+    // loss and the gradient row is zero
+    const bool valid = tgt >= 0 && tgt < K;
+    if (lane == 0 && valid) my_loss += (lse - (lb ? bf2f(lb[base + tgt]) : lf[base + tgt])) * gscale;
     if (db || df) {
-      const float inv = 1.f / s_all;
+      const float inv = valid ? 1.f / s_all : 0.f;
+      const float grad_scale = valid ? gscale : 0.f;
       if (VEC && lb && db) {
         const v4u* p = (const v4u*)(lb + base);
         v4u* o = (v4u*)(db + base);
@@ -655,7 +672,7 @@ __device__ __forceinline__ float seg_decay(const long* __restrict__ seg_off, con
 
 __global__ void sgd_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ mom,
                            bf16_t* __restrict__ w16, long n, const float* __restrict__ lr_dev, float lr, float wd,
-                           float momentum, float dampening, int nesterov, int first, const long* __restrict__ seg_off,
+                           float momentum, float omd, int nesterov, int first, const long* __restrict__ seg_off,
                            const float* __restrict__ seg_wd, int nseg, long base) {
   const float rate = lr_dev ? lr_dev[0] : lr;
   GRID_STRIDE(i, n) {
@@ -664,7 +681,7 @@ __global__ void sgd_kernel(float* __restrict__ w, const float* __restrict__ g, f
     if (nseg) decay += seg_decay(seg_off, seg_wd, nseg, base + i);
     float d = g[i] + decay * wi;
     if (momentum != 0.f) {
-      float b = first ? d : momentum * mom[i] + (1.f - dampening) * d;
+      float b = first ? d : momentum * mom[i] + omd * d;
       mom[i] = b;
       d = nesterov ? d + momentum * b : b;
     }
@@ -678,7 +695,7 @@ __global__ void sgd_kernel(float* __restrict__ w, const float* __restrict__ g, f
 // one binary search per 4 elements and then stepped forward (segments span thousands of elements).
 __global__ void sgd4_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ mom,
                             bf16_t* __restrict__ w16, long n4, const float* __restrict__ lr_dev, float lr, float wd,
-                            float momentum, float dampening, int nesterov, int first, const long* __restrict__ seg_off,
+                            float momentum, float omd, int nesterov, int first, const long* __restrict__ seg_off,
                             const float* __restrict__ seg_wd, int nseg, long base) {
   const float rate = lr_dev ? lr_dev[0] : lr;
   GRID_STRIDE(i, n4) {
@@ -705,7 +722,7 @@ __global__ void sgd4_kernel(float* __restrict__ w, const float* __restrict__ g, 
     for (int e = 0; e < 4; ++e) {
       float d = gv[e] + dec[e] * wv[e];
       if (momentum != 0.f) {
-        const float b = first ? d : momentum * mv[e] + (1.f - dampening) * d;
+        const float b = first ? d : momentum * mv[e] + omd * d;
         mo[e] = b;
         d = nesterov ? d + momentum * b : b;
       }
@@ -719,12 +736,12 @@ __global__ void sgd4_kernel(float* __restrict__ w, const float* __restrict__ g, 
 
 __global__ void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, bf16_t* __restrict__ w16, long n, float lr, float b1, float b2,
-                            float eps, float wd, float bc1, float bc2) {
+                            float omb1, float omb2, float eps, float wd, float bc1, float bc2) {
   GRID_STRIDE(i, n) {
     float wi = w[i];
     const float gi = g[i] + wd * wi;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi; v[i] = vi;
     // BigDL Adam: x -= lr * sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)
     wi -= lr * (sqrtf(bc2) / bc1) * mi / (sqrtf(vi) + eps);
@@ -813,21 +830,21 @@ __global__ void lstm_bwd_kernel(const float* __restrict__ act, const float* __re
 extern "C" {
 
 void bigdl_relu_fwd(const uint16_t* x, uint16_t* y, long n, hipStream_t st) {
-  const long n8 = n >> 3;
+  const long n8 = aligned16(x, y) ? n >> 3 : 0;
   if (n8) relu_fwd_kernel<<<grid_cap(n8), 256, 0, st>>>((const v4u*)x, (v4u*)y, n8);
-  if (n8 * 8 < n) relu_fwd_tail<<<1, 256, 0, st>>>(x, y, n8 * 8, n);
+  if (n8 * 8 < n) relu_fwd_tail<<<grid_cap(n - n8 * 8), 256, 0, st>>>(x, y, n8 * 8, n);
   HIP_LAUNCH_CHECK();
 }
 void bigdl_relu_bwd(const uint16_t* dy, const uint16_t* y, uint16_t* dx, long n, hipStream_t st) {
-  const long n8 = n >> 3;
+  const long n8 = aligned16(dy, y, dx) ? n >> 3 : 0;
   if (n8) relu_bwd_kernel<<<grid_cap(n8), 256, 0, st>>>((const v4u*)dy, (const v4u*)y, (v4u*)dx, n8);
-  if (n8 * 8 < n) relu_bwd_tail<<<1, 256, 0, st>>>(dy, y, dx, n8 * 8, n);
+  if (n8 * 8 < n) relu_bwd_tail<<<grid_cap(n - n8 * 8), 256, 0, st>>>(dy, y, dx, n8 * 8, n);
   HIP_LAUNCH_CHECK();
 }
 void bigdl_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* y, long n, hipStream_t st) {
-  const long n8 = n >> 3;
+  const long n8 = aligned16(a, b, y) ? n >> 3 : 0;
   if (n8) add_kernel<<<grid_cap(n8), 256, 0, st>>>((const v4u*)a, (const v4u*)b, (v4u*)y, n8);
-  if (n8 * 8 < n) add_tail<<<1, 256, 0, st>>>(a, b, y, n8 * 8, n);
+  if (n8 * 8 < n) add_tail<<<grid_cap(n - n8 * 8), 256, 0, st>>>(a, b, y, n8 * 8, n);
   HIP_LAUNCH_CHECK();
 }
 void bigdl_nchw_f32_to_nhwc_bf16(const float* x, uint16_t* y, int N, int C, int H, int W, int Cp, hipStream_t st) {
@@ -979,7 +996,11 @@ void bigdl_ones_col_acc(const float* gw, float* gW, float* gB, long N, int K, fl
   HIP_LAUNCH_CHECK();
 }
 void bigdl_cast_f32_bf16(const float* x, uint16_t* y, long n, hipStream_t st) {
-  cast_f32_bf16_kernel<<<grid_cap(n / 4 + 1), 256, 0, st>>>(x, y, n);
+  // scalar head up to x's next 16-byte boundary; y + h is then on an 8-byte boundary when x and y are views at the
+  // same element offset of aligned buffers (the exchange's g[lo:hi] / w16[lo:hi]); any other pairing goes all scalar
+  long h = (long)((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) / 4;
+  if ((reinterpret_cast<uintptr_t>(x) & 3) != 0 || (reinterpret_cast<uintptr_t>(y + h) & 7) != 0 || h > n) h = n;
+  cast_f32_bf16_kernel<<<grid_cap(h == n ? n : n / 4 + 4), 256, 0, st>>>(x, y, n, h);
   HIP_LAUNCH_CHECK();
 }
 void bigdl_cast_bf16_f32(const uint16_t* x, float* y, long n, hipStream_t st) {
@@ -1062,22 +1083,24 @@ void bigdl_softmax_xent(const uint16_t* lb, const float* lf, const float* labels
   HIP_LAUNCH_CHECK();
 }
 void bigdl_sgd_step(float* w, const float* g, float* mom, uint16_t* w16, long n, const float* lr_dev, float lr,
-                    float wd, float momentum, float dampening, int nesterov, int first, const long* seg_off,
+                    float wd, float momentum, double dampening, int nesterov, int first, const long* seg_off,
                     const float* seg_wd, int nseg, long base, hipStream_t st) {
+  const float omd = (float)(1.0 - dampening);   // narrowed once, from the double difference
   const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) |
                                       reinterpret_cast<uintptr_t>(mom)) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(w16) & 7) == 0;
   if (vec)
-    sgd4_kernel<<<grid_cap(n / 4), 256, 0, st>>>(w, g, mom, w16, n / 4, lr_dev, lr, wd, momentum, dampening, nesterov,
+    sgd4_kernel<<<grid_cap(n / 4), 256, 0, st>>>(w, g, mom, w16, n / 4, lr_dev, lr, wd, momentum, omd, nesterov,
                                                  first, seg_off, seg_wd, nseg, base);
   else
-    sgd_kernel<<<grid_cap(n), 256, 0, st>>>(w, g, mom, w16, n, lr_dev, lr, wd, momentum, dampening, nesterov, first,
+    sgd_kernel<<<grid_cap(n), 256, 0, st>>>(w, g, mom, w16, n, lr_dev, lr, wd, momentum, omd, nesterov, first,
                                             seg_off, seg_wd, nseg, base);
   HIP_LAUNCH_CHECK();
 }
-void bigdl_adam_step(float* w, const float* g, float* m, float* v, uint16_t* w16, long n, float lr, float beta1,
-                     float beta2, float eps, float wd, float bc1, float bc2, hipStream_t st) {
-  adam_kernel<<<grid_cap(n), 256, 0, st>>>(w, g, m, v, w16, n, lr, beta1, beta2, eps, wd, bc1, bc2);
+void bigdl_adam_step(float* w, const float* g, float* m, float* v, uint16_t* w16, long n, float lr, double beta1,
+                     double beta2, float eps, float wd, float bc1, float bc2, hipStream_t st) {
+  adam_kernel<<<grid_cap(n), 256, 0, st>>>(w, g, m, v, w16, n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1),
+                                           (float)(1.0 - beta2), eps, wd, bc1, bc2);
   HIP_LAUNCH_CHECK();
 }
 void bigdl_sumsq(const float* x, float* out, long n, hipStream_t st, float* det_ws) {

@@ -331,11 +331,13 @@ void bigdl_softmax_xent(const uint16_t* logits_bf16, const float* logits_f32, co
 #define BIGDL_XENT_SLOTS 2048
 
 // optimizers over flat fp32 buffers (optional bf16 shadow written in the same pass)
+// dampening, beta1, beta2 arrive as doubles: the kernels use 1 - dampening, 1 - beta narrowed once from the double
+// difference (1.f - 0.999f is 1.3e-5 off 0.001: 217 fp32 ulps on Adam's second moment)
 void bigdl_sgd_step(float* w, const float* g, float* mom, uint16_t* w16, long n, const float* lr_dev, float lr,
-                    float wd, float momentum, float dampening, int nesterov, int first, const long* seg_off,
+                    float wd, float momentum, double dampening, int nesterov, int first, const long* seg_off,
                     const float* seg_wd, int nseg, long base, hipStream_t st);
 void bigdl_adam_step(float* w, const float* g, float* m, float* v, uint16_t* w16, long n, float lr,
-                     float beta1, float beta2, float eps, float wd, float bc1, float bc2, hipStream_t st);
+                     double beta1, double beta2, float eps, float wd, float bc1, float bc2, hipStream_t st);
 void bigdl_sumsq(const float* x, float* out, long n, hipStream_t st, float* det_ws = nullptr);
 void bigdl_scale_f32(float* x, long n, const float* scale_dev, float scale, hipStream_t st);
 
@@ -615,7 +617,9 @@ int bigdl_kv_reorder(const uint16_t* src, uint16_t* dst, const int* parent, int 
 // 1 RMSprop (a = lr, b = decay rate, c = eps), 2 Adadelta (a = decay rate, b = eps), 3 Adamax (a = lr / (1 - b1^t),
 // b = b1, c = b2, d = eps), 4 Ftrl (a = lr, b = lr power, c = l1, d = l2, e = l2 shrinkage); s1 / s2 are the state
 // buffers (s2 may be null for Adagrad / RMSprop); w16 (optional) receives the bf16 copy of the updated weights.
-typedef struct { float a, b, c, d, e; } OptimHP;
+// om = 1 - decay rate of the moving average (RMSprop 1 - b, Adadelta 1 - a, Adamax 1 - b), narrowed from the double
+// difference by the caller.
+typedef struct { float a, b, c, d, e, om; } OptimHP;
 int bigdl_optim_step(int method, const OptimHP* hp, float* x, const float* g, float* s1, float* s2, uint16_t* w16,
                      long n, hipStream_t st);
 

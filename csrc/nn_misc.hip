@@ -415,9 +415,11 @@ void bigdl_log_softmax_bwd(const float* y, const float* gy, float* gx, long rows
   HIP_LAUNCH_CHECK();
 }
 void bigdl_f32_to_bf16_rtz(const float* x, uint16_t* y, long n, hipStream_t st) {
-  const long n4 = n >> 2;
+  // 16-byte loads / 8-byte stores only at aligned pointers; a view at an odd element offset goes scalar as a whole
+  const bool al = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0;
+  const long n4 = al ? n >> 2 : 0;
   if (n4) f32_to_bf16_rtz_kernel<<<blocks_for(n4), 256, 0, st>>>((const v4u*)x, (v2u*)y, n4);
-  if (n4 * 4 < n) f32_to_bf16_rtz_tail<<<1, 64, 0, st>>>((const unsigned*)x, y, n4 * 4, n);
+  if (n4 * 4 < n) f32_to_bf16_rtz_tail<<<al ? 1 : blocks_for(n), al ? 64 : 256, 0, st>>>((const unsigned*)x, y, n4 * 4, n);
   HIP_LAUNCH_CHECK();
 }
 

@@ -13,7 +13,7 @@ namespace {
 enum Method { M_ADAGRAD = 0, M_RMSPROP, M_ADADELTA, M_ADAMAX, M_FTRL };
 
 // per-method scalars: ADAGRAD (clr, wd); RMSPROP (clr, rho, eps); ADADELTA (rho, eps); ADAMAX (lr/(1-b1^t), b1, b2,
-// eps); FTRL (lr, power, l1, l2, l2shrink)
+// eps); FTRL (lr, power, l1, l2, l2shrink); om = 1 - the moving average's decay rate, from the double difference
 __device__ __forceinline__ void update1(int k, const OptimHP& h, float& x, float g, float& s1, float& s2) {
   switch (k) {
     case M_ADAGRAD: {
@@ -23,19 +23,19 @@ __device__ __forceinline__ void update1(int k, const OptimHP& h, float& x, float
       break;
     }
     case M_RMSPROP: {
-      s1 = h.b * s1 + (1.f - h.b) * g * g;
+      s1 = h.b * s1 + h.om * g * g;
       x -= h.a * g / (sqrtf(s1) + h.c);
       break;
     }
     case M_ADADELTA: {
-      s1 = h.a * s1 + (1.f - h.a) * g * g;
+      s1 = h.a * s1 + h.om * g * g;
       const float d = sqrtf(s2 + h.b) / sqrtf(s1 + h.b) * g;
       x -= d;
-      s2 = h.a * s2 + (1.f - h.a) * d * d;
+      s2 = h.a * s2 + h.om * d * d;
       break;
     }
     case M_ADAMAX: {
-      s1 = h.b * s1 + (1.f - h.b) * g;
+      s1 = h.b * s1 + h.om * g;
       s2 = fmaxf(h.c * s2, fabsf(g) + h.d);
       x -= h.a * s1 / s2;
       break;
