@@ -31,6 +31,8 @@ from .. import ops
 from ..ops import conv as cv
 from ..ops import conv_fn
 from ..ops import native
+from ..ops import sparse as sp
+from ..utils.table import Table
 from .abstractnn import AutogradModule, TensorModule
 from .init_methods import RandomUniform
 
@@ -281,12 +283,19 @@ class Linear(TensorModule):
 
 
 class SparseLinear(AutogradModule):
-    """Linear over a sparse (COO) input (reference SparseLinear.scala; wide & deep models)."""
+    """Linear over a sparse (COO) input (reference SparseLinear.scala; wide & deep models).
+
+    A sparse input runs on ``ops.sparse``: ``spmm`` forward, ``spmm_wgrad`` into gradWeight (only the columns that
+    occur), the bias gradient as the column sum of gradOutput. With ``backwardStart >= 0 and backwardLength > 0`` the
+    gradInput is the dense [B, backwardLength] product gradOutput @ weight[:, backwardStart - 1 : ... + backwardLength]
+    (1-based start, SparseLinear.scala:84-100: what a Wide & Deep graph passes on to its deep part); otherwise it is
+    the sparse gradient on the input's own pattern (``sddmm``). A dense input keeps the autograd path."""
 
     def __init__(self, inputSize, outputSize, withBias=True, backwardStart=-1, backwardLength=-1,
                  wRegularizer=None, bRegularizer=None, initWeight=None, initBias=None):
         super().__init__()
         self.inputSize, self.outputSize = inputSize, outputSize
+        self.backwardStart, self.backwardLength = int(backwardStart), int(backwardLength)
         self.register_parameter("weight", "gradWeight", torch.empty(outputSize, inputSize))
         if withBias:
             self.register_parameter("bias", "gradBias", torch.empty(outputSize))
@@ -296,6 +305,7 @@ class SparseLinear(AutogradModule):
         RandomUniform(-stdv, stdv).init(self.weight)
         if self.bias is not None:
             RandomUniform(-stdv, stdv).init(self.bias)
+        self._coo = None
 
     def fn(self, x):
         if x.is_sparse:
@@ -303,6 +313,57 @@ class SparseLinear(AutogradModule):
         else:
             y = x.float() @ self.weight.t()
         return y + self.bias if self.bias is not None else y
+
+    def _on_device_change(self):
+        self._coo = None
+
+    def _input_coo(self, input):
+        c = getattr(self, "_coo", None)
+        if c is None or c.src is not input:
+            c = self._coo = sp.Coo(input)
+        return c
+
+    def updateOutput(self, input):
+        if not (isinstance(input, torch.Tensor) and input.is_sparse):
+            self._coo = None
+            return super().updateOutput(input)
+        if input.dim() != 2 or input.shape[1] != self.inputSize:
+            raise ValueError(f"SparseLinear: expected a sparse [batch, {self.inputSize}] input, got {tuple(input.shape)}")
+        self._ag = self._pending_param_grads = None
+        with torch.no_grad():
+            return sp.spmm(self._input_coo(input), self.weight, self.bias)
+
+    def updateGradInput(self, input, gradOutput):
+        if not (isinstance(input, torch.Tensor) and input.is_sparse):
+            return super().updateGradInput(input, gradOutput)
+        with torch.no_grad():
+            gy = gradOutput.to(self.weight.dtype)
+            if self.backwardStart >= 0 and self.backwardLength > 0:
+                s = self.backwardStart - 1
+                w = self.weight[:, s:s + self.backwardLength]
+                if gy.is_cuda and w.is_cuda and w.dtype == torch.float32:
+                    from ..ops import tensor_math as tm      # strided fp32 GEMM (csrc/tensor_math.hip): no weight copy
+
+                    out = torch.empty(gy.shape[0], w.shape[1], dtype=torch.float32, device=gy.device)
+                    return tm.gemm(out, gy.contiguous(), w)
+                return gy @ w
+            c = self._input_coo(input)
+            return c.with_values(sp.sddmm(c, gy, self.weight))
+
+    def accGradParameters(self, input, gradOutput):
+        if not (isinstance(input, torch.Tensor) and input.is_sparse):
+            return super().accGradParameters(input, gradOutput)
+        with torch.no_grad():
+            gy = gradOutput.to(self.weight.dtype)
+            if self.scaleW != 0:
+                sp.spmm_wgrad(self._input_coo(input), gy, self.gradWeight, self.scaleW)
+            if self.bias is not None and self.scaleB != 0:
+                if gy.is_cuda and self.gradBias.is_cuda:
+                    from ..ops import tensor_math as tm
+
+                    self.gradBias.add_(tm.reduce(gy, tm.R_SUM, 0)[0].view(-1), alpha=self.scaleB)
+                else:
+                    self.gradBias.add_(gy.sum(0), alpha=self.scaleB)
 
 
 class Bilinear(AutogradModule):
@@ -412,12 +473,19 @@ class LookupTable(TensorModule):
 
 
 class LookupTableSparse(AutogradModule):
-    """Sparse-id embedding with ``combiner`` in {sum, mean, sqrtn} (reference LookupTableSparse.scala:47)."""
+    """Sparse-id embedding with ``combiner`` in {sum, mean, sqrtn} (reference LookupTableSparse.scala:47).
+
+    The input is one sparse [B, L] tensor of 1-based ids, or a Table of ids and per-id weights on the same pattern.
+    Sparse inputs run on ``ops.sparse.lookup_sparse`` / ``lookup_sparse_backward``; the input is not differentiable
+    (LookupTableSparse.scala:161-164), so gradInput is zero-valued tensors on the inputs' patterns. Dense id tensors
+    keep the autograd path. ``maxNorm`` is accepted and ignored: its renormalisation and gradient are not
+    implemented."""
 
     def __init__(self, nIndex, nOutput, combiner="sum", maxNorm=-1.0, wRegularizer=None):
         super().__init__()
         self.combiner = combiner
         self.register_parameter("weight", "gradWeight", torch.empty(nIndex, nOutput).normal_(0, 1))
+        self._fwd = None
 
     def fn(self, x):
         ids, weights = (x[1], x[2]) if not isinstance(x, torch.Tensor) else (x, None)
@@ -432,6 +500,53 @@ class LookupTableSparse(AutogradModule):
         elif self.combiner == "sqrtn":
             s = s / (w * w).sum(1, keepdim=True).sqrt().clamp_min(1e-12)
         return s
+
+    def _on_device_change(self):
+        self._fwd = None
+
+    @staticmethod
+    def _split(x):
+        return (x[1], x[2]) if not isinstance(x, torch.Tensor) else (x, None)
+
+    def _sparse_in(self, input):
+        ids, weights = self._split(input)
+        return ids.is_sparse and (weights is None or weights.is_sparse)
+
+    def _forward_state(self, input):
+        st = getattr(self, "_fwd", None)
+        if st is None or st[0] is not input:
+            ids, weights = self._split(input)
+            with torch.no_grad():
+                ci, cw = sp.Coo(ids), (None if weights is None else sp.Coo(weights))
+                out, scales = sp.lookup_sparse(ci, cw, self.weight, self.combiner)
+            st = self._fwd = (input, ci, cw, scales, out)
+        return st
+
+    def updateOutput(self, input):
+        if not self._sparse_in(input):
+            self._fwd = None
+            return super().updateOutput(input)
+        self._ag = self._pending_param_grads = self._fwd = None
+        return self._forward_state(input)[4]
+
+    def updateGradInput(self, input, gradOutput):
+        if not self._sparse_in(input):
+            return super().updateGradInput(input, gradOutput)
+        _, ci, cw, _, _ = self._forward_state(input)
+        zero = lambda c: c.with_values(torch.zeros_like(c.vals))      # noqa: E731
+        if isinstance(input, torch.Tensor):
+            return zero(ci)
+        out = Table()
+        out[1], out[2] = zero(ci), zero(cw)
+        return out
+
+    def accGradParameters(self, input, gradOutput):
+        if not self._sparse_in(input):
+            return super().accGradParameters(input, gradOutput)
+        _, ci, cw, scales, _ = self._forward_state(input)
+        with torch.no_grad():
+            gy = gradOutput.to(self.weight.dtype)
+            sp.lookup_sparse_backward(ci, cw, scales, gy, self.gradWeight, self.scaleW)
 
 
 class MM(AutogradModule):

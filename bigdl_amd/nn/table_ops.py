@@ -277,7 +277,12 @@ class SparseJoinTable(TensorModule):
         self.dimension = dimension
 
     def updateOutput(self, input):
-        return torch.cat([t.to_dense() for t in input.toSeq()], dim=self.dimension - 1).to_sparse()
+        ts = input.toSeq()
+        if self.dimension == 2 and all(t.is_sparse and t.dim() == 2 for t in ts):
+            from ..ops import sparse as sp      # index-list join (csrc/sparse.hip) on the GPU engine, this math elsewhere
+
+            return sp.concat_cols(ts)
+        return torch.cat([t.to_dense() for t in ts], dim=self.dimension - 1).to_sparse()
 
     def updateGradInput(self, input, gradOutput):
         return None

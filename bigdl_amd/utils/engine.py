@@ -175,6 +175,10 @@ class _Engine:
             from ..ops import detection
 
             detection.set_batched(v)
+        elif k == "bigdl.sparse.native":            # SparseLinear / LookupTableSparse / SparseJoinTable kernels
+            from ..ops import sparse
+
+            sparse.set_native(v)
         elif k == "bigdl.module.deviceTiming":      # getTimes in device time (HIP events) for GPU modules
             from ..nn import abstractnn
 

@@ -1465,6 +1465,145 @@ void embedding_bwd_ids(const Tensor& gout, const Tensor& ids, const Tensor& gW, 
   bigdl_embedding_bwd_ids(gout.data_ptr(), gb ? 1 : 0, ids.data_ptr(), il ? 1 : 0, mf(gW, "gW"), ids.numel(), gW.size(1),
                           gW.size(0), pad, (float)scale, stream());
 }
+// ---------------------------------------------------------------------------------------------- sparse COO (csrc/sparse.hip)
+// idx = the [2, nnz] int64 index tensor of a coalesced 2-D sparse tensor, vals = its fp32 values, offs = int32 [B + 1]
+struct Coo {
+  const long* rows;
+  const long* cols;
+  int64_t nnz;
+};
+Coo coo_idx(const Tensor& idx, const char* n) {
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kLong && idx.dim() == 2 && idx.size(0) == 2 && idx.is_contiguous(),
+              n, ": indices must be a contiguous int64 [2, nnz] device tensor");
+  TORCH_CHECK(idx.size(1) < (1L << 31), n, ": nnz must be below 2^31");
+  const long* p = (const long*)idx.data_ptr();
+  return {p, p + idx.size(1), idx.size(1)};
+}
+const int* coo_offs(const Tensor& offs, int64_t B, const char* n) {
+  TORCH_CHECK(offs.is_cuda() && offs.scalar_type() == at::kInt && offs.is_contiguous() && offs.numel() == B + 1 &&
+              B < (1L << 31) - 1, n, ": offsets must be a contiguous int32 [B + 1] device tensor");
+  return (const int*)offs.data_ptr();
+}
+const float* coo_vals(const Tensor& v, int64_t nnz, const char* n) {
+  check_f32(v, n);
+  TORCH_CHECK(v.numel() == nnz, n, ": one value per entry");
+  return (const float*)v.data_ptr();
+}
+// stable sort of `keys` with the entries to skip (valid == false) set to -1: (sorted keys, entry numbers)
+std::pair<Tensor, Tensor> sorted_keys(const Tensor& keys, const Tensor& valid) {
+  auto sorted = at::sort(keys.masked_fill(valid.logical_not(), -1), /*stable=*/true, /*dim=*/0, /*descending=*/false);
+  return {std::get<0>(sorted).contiguous(), std::get<1>(sorted).contiguous()};
+}
+
+void coo_row_offsets(const Tensor& idx, const Tensor& offs) {
+  const Coo c = coo_idx(idx, "coo_row_offsets");
+  const int64_t B = offs.numel() - 1;
+  TORCH_CHECK(B >= 0, "coo_row_offsets: offsets [B + 1]");
+  bigdl_coo_row_offsets(c.rows, c.nnz, (int)B, const_cast<int*>(coo_offs(offs, B, "coo_row_offsets")), stream());
+}
+void spmm_fwd(const Tensor& idx, const Tensor& vals, const Tensor& offs, const Tensor& W, const OptT& bias,
+              const Tensor& y) {
+  const Coo c = coo_idx(idx, "spmm_fwd");
+  check_f32(W, "spmm_fwd W"); check_f32(y, "spmm_fwd y");
+  TORCH_CHECK(W.dim() == 2 && y.dim() == 2 && y.size(1) == W.size(0) && W.size(0) < (1L << 31), "spmm_fwd: W [N, D], y [B, N]");
+  const int64_t B = y.size(0), N = W.size(0);
+  if (bias && bias->defined()) { check_f32(*bias, "spmm_fwd bias"); TORCH_CHECK(bias->numel() == N, "spmm_fwd: bias [N]"); }
+  TORCH_CHECK(c.nnz > 0, "spmm_fwd: an empty input is answered by the caller");
+  bigdl_spmm_fwd(c.cols, coo_vals(vals, c.nnz, "spmm_fwd values"), coo_offs(offs, B, "spmm_fwd"), cf(W, "W"),
+                 ocf(bias, "bias"), mf(y, "y"), (int)B, (int)N, W.size(1), stream());
+}
+// returns the route: 0 = fp32 atomics, 1 = ordered (deterministic mode)
+int64_t spmm_wgrad(const Tensor& idx, const Tensor& vals, const Tensor& gy, const Tensor& gW, double scale) {
+  const Coo c = coo_idx(idx, "spmm_wgrad");
+  check_f32(gy, "spmm_wgrad gy"); check_f32(gW, "spmm_wgrad gW");
+  TORCH_CHECK(gy.dim() == 2 && gW.dim() == 2 && gy.size(1) == gW.size(0) && gW.size(0) < (1L << 31) &&
+              gy.size(0) < (1L << 31), "spmm_wgrad: gy [B, N], gW [N, D]");
+  const int64_t B = gy.size(0), N = gW.size(0), D = gW.size(1);
+  const float* v = coo_vals(vals, c.nnz, "spmm_wgrad values");
+  TORCH_CHECK(c.nnz > 0, "spmm_wgrad: an empty input is answered by the caller");
+  if (bigdl_deterministic()) {
+    const Tensor rows = idx.select(0, 0), cols = idx.select(0, 1);
+    const auto kp = sorted_keys(cols, rows.ge(0).logical_and(rows.lt(B)).logical_and(cols.ge(0)).logical_and(cols.lt(D)));
+    bigdl_spmm_wgrad_sorted((const long*)kp.first.data_ptr(), (const long*)kp.second.data_ptr(), c.rows, v, cf(gy, "gy"),
+                            mf(gW, "gW"), c.nnz, (int)B, (int)N, D, (float)scale, stream());
+    return 1;
+  }
+  bigdl_spmm_wgrad(c.rows, c.cols, v, cf(gy, "gy"), mf(gW, "gW"), c.nnz, (int)B, (int)N, D, (float)scale, stream());
+  return 0;
+}
+void sddmm_rows(const Tensor& idx, const Tensor& gy, const Tensor& W, const Tensor& g) {
+  const Coo c = coo_idx(idx, "sddmm_rows");
+  check_f32(gy, "sddmm_rows gy"); check_f32(W, "sddmm_rows W"); check_f32(g, "sddmm_rows g");
+  TORCH_CHECK(gy.dim() == 2 && W.dim() == 2 && gy.size(1) == W.size(0) && g.numel() == c.nnz &&
+              W.size(0) < (1L << 31) && gy.size(0) < (1L << 31), "sddmm_rows: gy [B, N], W [N, D], g [nnz]");
+  TORCH_CHECK(c.nnz > 0, "sddmm_rows: an empty input is answered by the caller");
+  bigdl_sddmm_rows(c.rows, c.cols, cf(gy, "gy"), cf(W, "W"), mf(g, "g"), c.nnz, (int)gy.size(0), (int)W.size(0),
+                   W.size(1), stream());
+}
+void lookup_sparse_fwd(const Tensor& offs, const Tensor& ids, const OptT& wts, const Tensor& W, int64_t combiner,
+                       const Tensor& out, const Tensor& scales) {
+  check_f32(ids, "lookup_sparse_fwd ids"); check_f32(W, "lookup_sparse_fwd W"); check_f32(out, "lookup_sparse_fwd out");
+  check_f32(scales, "lookup_sparse_fwd scales");
+  TORCH_CHECK(W.dim() == 2 && out.dim() == 2 && out.size(1) == W.size(1) && scales.numel() == out.size(0) &&
+              W.size(1) < (1L << 31) && combiner >= 0 && combiner <= 2, "lookup_sparse_fwd: W [nIndex, nOut], out [B, nOut]");
+  TORCH_CHECK(ids.numel() > 0 && ids.numel() < (1L << 31), "lookup_sparse_fwd: an empty input is answered by the caller");
+  if (wts && wts->defined()) coo_vals(*wts, ids.numel(), "lookup_sparse_fwd weights");
+  bigdl_lookup_sparse_fwd(coo_offs(offs, out.size(0), "lookup_sparse_fwd"), cf(ids, "ids"), ocf(wts, "weights"), cf(W, "W"),
+                          mf(out, "out"), mf(scales, "scales"), (int)out.size(0), (int)W.size(1), W.size(0),
+                          (int)combiner, stream());
+}
+int64_t lookup_sparse_bwd(const Tensor& idx, const Tensor& offs, const Tensor& ids, const OptT& wts, const Tensor& scales,
+                          const Tensor& gy, const Tensor& gW, double scale) {
+  const Coo c = coo_idx(idx, "lookup_sparse_bwd");
+  check_f32(scales, "lookup_sparse_bwd scales"); check_f32(gy, "lookup_sparse_bwd gy"); check_f32(gW, "lookup_sparse_bwd gW");
+  TORCH_CHECK(gy.dim() == 2 && gW.dim() == 2 && gy.size(1) == gW.size(1) && scales.numel() == gy.size(0) &&
+              gW.size(1) < (1L << 31), "lookup_sparse_bwd: gy [B, nOut], gW [nIndex, nOut], scales [B]");
+  const int64_t B = gy.size(0), nOut = gW.size(1), nIndex = gW.size(0);
+  const float* idp = coo_vals(ids, c.nnz, "lookup_sparse_bwd ids");
+  if (wts && wts->defined()) coo_vals(*wts, c.nnz, "lookup_sparse_bwd weights");
+  const int* op = coo_offs(offs, B, "lookup_sparse_bwd");
+  TORCH_CHECK(c.nnz > 0, "lookup_sparse_bwd: an empty input is answered by the caller");
+  if (bigdl_deterministic()) {
+    const Tensor rows = idx.select(0, 0);
+    const Tensor key = ids.to(at::kLong) - 1;          // the kernels' (long)id - 1
+    const auto kp = sorted_keys(key, rows.ge(0).logical_and(rows.lt(B)).logical_and(key.ge(0)).logical_and(key.lt(nIndex)));
+    bigdl_lookup_sparse_bwd_sorted((const long*)kp.first.data_ptr(), (const long*)kp.second.data_ptr(), c.rows,
+                                   ocf(wts, "weights"), cf(scales, "scales"), cf(gy, "gy"), mf(gW, "gW"), c.nnz, (int)B,
+                                   (int)nOut, nIndex, (float)scale, stream());
+    return 1;
+  }
+  bigdl_lookup_sparse_bwd(op, idp, ocf(wts, "weights"), cf(scales, "scales"), cf(gy, "gy"), mf(gW, "gW"), (int)B,
+                          (int)nOut, nIndex, (float)scale, stream());
+  return 0;
+}
+// widths = D_i; out_idx [2, total] int64 and out_vals [total] fp32 are zero-filled by the caller (slots that entries
+// with an out-of-range row would have taken stay zero)
+void sparse_concat_cols(std::vector<Tensor> idxs, std::vector<Tensor> vals, std::vector<Tensor> offs,
+                        std::vector<int64_t> widths, const Tensor& out_idx, const Tensor& out_vals) {
+  const size_t n = idxs.size();
+  TORCH_CHECK(n >= 1 && n <= BIGDL_SPARSE_MAX_JOIN && vals.size() == n && offs.size() == n && widths.size() == n,
+              "sparse_concat_cols: 1 to 8 inputs");
+  const Coo o = coo_idx(out_idx, "sparse_concat_cols out");
+  const int64_t B = offs[0].numel() - 1;
+  SparseJoinInputs in{};
+  in.n = (int)n;
+  int64_t total = 0, shift = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const Coo c = coo_idx(idxs[i], "sparse_concat_cols input");
+    in.cols[i] = c.cols;
+    in.vals[i] = coo_vals(vals[i], c.nnz, "sparse_concat_cols values");
+    in.offs[i] = coo_offs(offs[i], B, "sparse_concat_cols");
+    in.shift[i] = shift;
+    shift += widths[i];
+    total += c.nnz;
+  }
+  TORCH_CHECK(total == o.nnz && total > 0, "sparse_concat_cols: out holds the sum of the inputs' nnz (> 0)");
+  const int rc = bigdl_sparse_concat_cols(&in, (int)B, const_cast<long*>(o.rows), const_cast<long*>(o.cols),
+                                          const_cast<float*>(coo_vals(out_vals, total, "sparse_concat_cols out values")),
+                                          total, stream());
+  TORCH_CHECK(rc == 0, "sparse_concat_cols failed");
+}
+
 void resize_bilinear_fwd(const Tensor& x, const Tensor& y, double sh, double sw) {
   contig(x, "x"); contig(y, "y");
   TORCH_CHECK(x.dim() == 4 && y.dim() == 4 && x.size(0) * x.size(1) == y.size(0) * y.size(1), "resize: shapes");
@@ -2058,6 +2197,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embedding_bwd", &embedding_bwd);
   m.def("embedding_fwd_ids", &embedding_fwd_ids);
   m.def("embedding_bwd_ids", &embedding_bwd_ids);
+  m.def("coo_row_offsets", &coo_row_offsets);
+  m.def("spmm_fwd", &spmm_fwd);
+  m.def("spmm_wgrad", &spmm_wgrad);
+  m.def("sddmm_rows", &sddmm_rows);
+  m.def("lookup_sparse_fwd", &lookup_sparse_fwd);
+  m.def("lookup_sparse_bwd", &lookup_sparse_bwd);
+  m.def("sparse_concat_cols", &sparse_concat_cols);
   m.def("resize_bilinear_fwd", &resize_bilinear_fwd);
   m.def("resize_bilinear_bwd", &resize_bilinear_bwd);
   m.def("log_softmax_fwd", &log_softmax_fwd);

@@ -518,6 +518,46 @@ void bigdl_log_softmax_fwd(const float* x, float* y, long rows, int cols, hipStr
 void bigdl_log_softmax_bwd(const float* y, const float* gy, float* gx, long rows, int cols, hipStream_t st);
 void bigdl_f32_to_bf16_rtz(const float* x, uint16_t* y, long n, hipStream_t st);
 
+// Sparse COO kernels (csrc/sparse.hip) over a coalesced 2-D tensor [B, D]: rows / cols = the two int64 index rows
+// [nnz] in row-major order, vals fp32 [nnz], offs = int32 CSR offsets [B + 1] from bigdl_coo_row_offsets (nnz < 2^31).
+// Entries with a row outside [0, B), a column outside [0, D) or an id outside [1, nIndex] contribute nothing.
+void bigdl_coo_row_offsets(const long* rows, long nnz, int B, int* offs, hipStream_t st);
+// y[b, o] = bias[o] + sum_k val_k W[o, col_k] over row b's entries; W [N, D] as stored, bias [N] or null
+void bigdl_spmm_fwd(const long* cols, const float* vals, const int* offs, const float* W, const float* bias, float* y,
+                    int B, int N, long D, hipStream_t st);
+// gW[o, col_k] += scale val_k gy[row_k, o]: fp32 atomics, or (sorted) keys = the columns stably sorted with -1 for
+// entries to skip, pos = the matching entry numbers, one in-order sum and one plain store per (o, column)
+void bigdl_spmm_wgrad(const long* rows, const long* cols, const float* vals, const float* gy, float* gW, long nnz,
+                      int B, int N, long D, float scale, hipStream_t st);
+void bigdl_spmm_wgrad_sorted(const long* keys, const long* pos, const long* rows, const float* vals, const float* gy,
+                             float* gW, long nnz, int B, int N, long D, float scale, hipStream_t st);
+// g[k] = sum_o gy[row_k, o] W[o, col_k]: the gradient values on the input's own pattern (0 for a skipped entry)
+void bigdl_sddmm_rows(const long* rows, const long* cols, const float* gy, const float* W, float* g, long nnz, int B,
+                      int N, long D, hipStream_t st);
+// out[b, :] = s_b sum_k w_k W[id_k - 1, :]; ids = fp32 1-based ids on the pattern, wts = weights on the same pattern
+// or null (w = 1); combiner 0 sum (s = 1), 1 mean (1 / sum w), 2 sqrtn (1 / sqrt(sum w^2)), sums over in-range ids
+// only, s = 0 for an empty row; scales [B] receives s_b for the backward.
+void bigdl_lookup_sparse_fwd(const int* offs, const float* ids, const float* wts, const float* W, float* out,
+                             float* scales, int B, int nOut, long nIndex, int combiner, hipStream_t st);
+// gW[id_k - 1, :] += scale s_b w_k gy[b, :]: atomics, or (sorted) keys = id - 1 stably sorted with -1 to skip
+void bigdl_lookup_sparse_bwd(const int* offs, const float* ids, const float* wts, const float* scales, const float* gy,
+                             float* gW, int B, int nOut, long nIndex, float scale, hipStream_t st);
+void bigdl_lookup_sparse_bwd_sorted(const long* keys, const long* pos, const long* rows, const float* wts,
+                                    const float* scales, const float* gy, float* gW, long nnz, int B, int nOut,
+                                    long nIndex, float scale, hipStream_t st);
+// Join of up to 8 coalesced inputs [B, D_i] along the columns: output row b = the inputs' row-b segments in input
+// order with columns shifted by shift[i] = sum_{j<i} D_j. total = sum of the inputs' nnz = the output's capacity.
+#define BIGDL_SPARSE_MAX_JOIN 8
+struct SparseJoinInputs {
+  const long* cols[BIGDL_SPARSE_MAX_JOIN];
+  const float* vals[BIGDL_SPARSE_MAX_JOIN];
+  const int* offs[BIGDL_SPARSE_MAX_JOIN];
+  long shift[BIGDL_SPARSE_MAX_JOIN];
+  int n;
+};
+int bigdl_sparse_concat_cols(const SparseJoinInputs* in, int B, long* out_rows, long* out_cols, float* out_vals,
+                             long total, hipStream_t st);
+
 // Fused LSTM steps (csrc/lstm.hip) with optional peepholes, optional row mask and a caller-given gate layout. W16
 // [4H][H] bf16, WT16 = W^T [H][4H] bf16. Row strides: xg/h_out/acts/dout/dg_out rows are batch rows (ldx, ldh, lda,
 // ldd, ldg elements apart). gi, gf, gg, go: positions (a permutation of 0..3) of the i, f, g, o blocks in the [4H]
