@@ -295,6 +295,18 @@ class LarsSGD(SGD):
 
     def optimize(self, feval, x):
         fx, g = feval(x)
+        from ..ops import lars
+
+        if self._calculated_scale is None and getattr(self, "_wd_segments", None) is None and native_ok(x, g) \
+                and lars.fused(True):
+            # stand-alone on the GPU: a cached one-piece plan, norms then update (csrc/lars.hip), nothing read back
+            plan = lars.one_piece_plan(self, x)
+            if plan.usable(x, g, self._shadow16):
+                plan.norms(x, g)
+                plan.advance()
+                plan.update(x, g, self._shadow16, self.weightDecay)
+                return x, [fx]
+        lars._set_route("loop")
         v = _state(self, "v", x)
         self.learningRateSchedule.updateHyperParameter(self)
         global_lr = -self.learningRateSchedule.currentRate * self.trust

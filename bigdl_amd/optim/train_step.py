@@ -278,7 +278,8 @@ class TrainStep:
         if lars:
             from ..parallel.processors import LarsProcessor
 
-            self.processors.append(LarsProcessor(lars[0][3].weightDecay))
+            self._lars_processor = LarsProcessor(lars[0][3].weightDecay)
+            self.processors.append(self._lars_processor)
         self.loss = None
         # ParallelOptimizer-style bucketed reduce-scatter overlapped with backward (parallel/bucketed.py)
         if overlap is None:
@@ -292,6 +293,7 @@ class TrainStep:
         else:
             owned = [(self.comm.start, self.comm.end)]
         self.plan = build_update_plan(owned, self.splits, self.w16, self.seg)
+        self.lars_plan = self._build_lars_plan()
         self._pending_gather = False
         from .phase_timer import PhaseTimer
 
@@ -372,9 +374,36 @@ class TrainStep:
         for proc in self.processors:
             proc(self)
 
+    def _build_lars_plan(self):
+        """Fused LARS (ops/lars.py): one plan over this rank's LarsSGD pieces, layer ids in ``splits`` order on every
+        rank so the all-reduce of the layer sums lines up. None keeps the per-layer route: the CPU engine, the switch
+        off, folded regularizers (``seg``) or buffers the kernels do not take."""
+        from ..ops import lars
+        from .methods import LarsSGD
+        from .optim_method import native_ok
+
+        pieces = [p for p in self.plan if isinstance(p.method, LarsSGD)]
+        if not pieces or self.device.type != "cuda" or self.seg is not None or not lars.fused(True) \
+                or not native_ok(self.w, self.g):
+            return None
+        names = [s[0] for s in self.splits if isinstance(s[3], LarsSGD)]
+        idx = {n: i for i, n in enumerate(names)}
+        self._other_pieces = [p for p in self.plan if not isinstance(p.method, LarsSGD)]
+        return lars.LarsPlan([(p.lo, p.hi, idx[p.name], p.method) for p in pieces], len(names), self.device,
+                             phase=lars.phase_of(self.w))
+
     def optimize_pieces(self, loss, pieces=None, g=None):
         self._lockstep()
         g = self.g if g is None else g
+        lp = self.lars_plan
+        if lp is not None and pieces is None and lp.usable(self.w, g, self.w16):
+            # every LarsSGD piece in one launch; g is read here, at call time (the straggler path passes another)
+            if not lp.acc_fresh:                # the processors did not run on this gradient
+                lp.norms(self.w, g)
+                self.comm.all_reduce_scalar(lp.acc)
+            lp.advance()
+            lp.update(self.w, g, self.w16, self._lars_processor.weightDecay)
+            pieces = self._other_pieces
         for p in (self.plan if pieces is None else pieces):
             gs = g[p.lo:p.hi]
             p.method.optimize(lambda _x, _g=gs: (loss, _g), self.w[p.lo:p.hi])

@@ -110,6 +110,14 @@ class LarsProcessor(ParameterProcessor):
     def collectGlobalData(self, step, state):
         from ..optim.methods import LarsSGD
 
+        plan = getattr(step, "lars_plan", None)
+        if plan is not None and plan.usable(step.w, step.g, step.w16):
+            # fused route (ops/lars.py): the chunk partials and the per-layer sums in two launches, one all-reduce of
+            # the 2 x L sums; the guards and the rates are applied inside the update kernel
+            plan.norms(step.w, step.g)
+            step.comm.all_reduce_scalar(plan.acc)
+            state["larsPlan"] = plan
+            return
         names = [s[0] for s in step.splits if isinstance(s[3], LarsSGD)]
         idx = {n: i for i, n in enumerate(names)}
         acc = ops.zeros(2 * len(names), device=step.device)
@@ -130,6 +138,8 @@ class LarsProcessor(ParameterProcessor):
         state["larsScale"] = {n: scale[i] for n, i in idx.items()}
 
     def processParameters(self, step, state):
+        if "larsPlan" in state:             # the update kernel reads the sums itself
+            return
         sc = state["larsScale"]
         for p in step.plan:
             if p.name in sc:

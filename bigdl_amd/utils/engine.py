@@ -175,6 +175,10 @@ class _Engine:
             from ..ops import detection
 
             detection.set_batched(v)
+        elif k == "bigdl.lars.fused":               # every LarsSGD layer's norms and update in three launches
+            from ..ops import lars
+
+            lars.set_fused(v)
         elif k == "bigdl.sparse.native":            # SparseLinear / LookupTableSparse / SparseJoinTable kernels
             from ..ops import sparse
 

@@ -798,6 +798,53 @@ void optim_step(int64_t method, const Tensor& x, const Tensor& g, const Tensor& 
   TORCH_CHECK(bigdl_optim_step((int)method, &hp, mf(x, "x"), cf(g, "g"), mf(s1, "s1"), omf(s2, "s2"),
                                ombf(w16, "w16"), x.numel(), stream()) == 0, "optim_step: unknown method");
 }
+// Fused LARS (csrc/lars.hip). The tables live on the device, so their contents cannot be checked here: the caller
+// (bigdl_amd/ops/lars.py build_tables) passes the extents they imply, max_hi (largest piece end) and v_need (momentum
+// elements addressed), and those are held against the buffers.
+struct LarsTables {
+  const int* chunk_piece; const long* chunk_start; const long* piece_tab; int nchunks; int npieces;
+};
+LarsTables lars_tables(const Tensor& chunk_piece, const Tensor& chunk_start, const Tensor& piece_tab) {
+  TORCH_CHECK(chunk_piece.is_cuda() && chunk_start.is_cuda() && piece_tab.is_cuda(), "lars: tables must be GPU tensors");
+  TORCH_CHECK(chunk_piece.scalar_type() == at::kInt && chunk_start.scalar_type() == at::kLong &&
+                  piece_tab.scalar_type() == at::kLong, "lars: chunk_piece int32, chunk_start / piece_tab int64");
+  TORCH_CHECK(chunk_piece.is_contiguous() && chunk_start.is_contiguous() && piece_tab.is_contiguous(),
+              "lars: tables must be contiguous");
+  TORCH_CHECK(chunk_start.numel() == chunk_piece.numel() && piece_tab.numel() % 4 == 0, "lars: table sizes");
+  return {(const int*)chunk_piece.data_ptr(), (const long*)chunk_start.data_ptr(), (const long*)piece_tab.data_ptr(),
+          (int)chunk_piece.numel(), (int)(piece_tab.numel() / 4)};
+}
+void lars_norms(const Tensor& w, const Tensor& g, const Tensor& chunk_piece, const Tensor& chunk_start,
+                const Tensor& piece_tab, const Tensor& layer_chunks, const Tensor& ws, const Tensor& acc,
+                int64_t max_hi) {
+  const LarsTables t = lars_tables(chunk_piece, chunk_start, piece_tab);
+  TORCH_CHECK(layer_chunks.is_cuda() && layer_chunks.scalar_type() == at::kInt && layer_chunks.is_contiguous() &&
+                  layer_chunks.numel() % 2 == 0, "lars_norms: layer_chunks must be a contiguous int32 [L][2] GPU tensor");
+  const int nlayers = (int)(layer_chunks.numel() / 2);
+  TORCH_CHECK(w.is_contiguous() && g.is_contiguous() && ws.is_contiguous() && acc.is_contiguous(),
+              "lars_norms: contiguous buffers");
+  TORCH_CHECK(max_hi >= 0 && w.numel() >= max_hi && g.numel() >= max_hi, "lars_norms: w / g shorter than the pieces");
+  TORCH_CHECK(ws.numel() >= 2 * (int64_t)t.nchunks && acc.numel() >= 2 * (int64_t)nlayers,
+              "lars_norms: workspace holds 2 floats per chunk, acc 2 per layer");
+  TORCH_CHECK(bigdl_lars_norms(cf(w, "w"), cf(g, "g"), t.chunk_piece, t.chunk_start, t.piece_tab,
+                               (const int*)layer_chunks.data_ptr(), mf(ws, "ws"), mf(acc, "acc"), t.nchunks, nlayers,
+                               stream()) == 0, "lars_norms: w and g must share one 16-byte phase");
+}
+void lars_update(const Tensor& w, const Tensor& g, const Tensor& v, const OptT& w16, const Tensor& chunk_piece,
+                 const Tensor& chunk_start, const Tensor& piece_tab, const Tensor& piece_hp, const Tensor& rates,
+                 const Tensor& acc, double WD, int64_t max_hi, int64_t v_need, int64_t nlayers) {
+  const LarsTables t = lars_tables(chunk_piece, chunk_start, piece_tab);
+  TORCH_CHECK(w.is_contiguous() && g.is_contiguous() && v.is_contiguous() && piece_hp.is_contiguous() &&
+                  rates.is_contiguous() && acc.is_contiguous() && (!(w16 && w16->defined()) || w16->is_contiguous()),
+              "lars_update: contiguous buffers");
+  TORCH_CHECK(max_hi >= 0 && w.numel() >= max_hi && g.numel() >= max_hi && v_need >= 0 && v.numel() >= v_need &&
+                  (!(w16 && w16->defined()) || w16->numel() >= max_hi), "lars_update: buffers shorter than the pieces");
+  TORCH_CHECK(piece_hp.numel() == 2 * (int64_t)t.npieces && rates.numel() >= t.npieces && nlayers >= 0 &&
+                  acc.numel() >= 2 * nlayers, "lars_update: piece_hp [P][2], rates [P], acc [L][2]");
+  TORCH_CHECK(bigdl_lars_update(mf(w, "w"), cf(g, "g"), mf(v, "v"), ombf(w16, "w16"), t.chunk_piece, t.chunk_start,
+                                t.piece_tab, cf(piece_hp, "piece_hp"), cf(rates, "rates"), cf(acc, "acc"), WD,
+                                t.nchunks, stream()) == 0, "lars_update: w, g, v and w16 must share one 16-byte phase");
+}
 // workspace = false: deterministic mode without its slot workspace (the one-block form of bigdl_sumsq, which the C
 // entry point keeps for callers without an allocator). No caller in bigdl_amd/ passes it: the argument exists so that
 // tests/test_step_tail_edges_gpu.py can reach that form.
@@ -2105,6 +2152,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("STAT_SLOTS") = BIGDL_STAT_SLOTS;
   m.attr("DET_SLOTS") = BIGDL_DET_SLOTS;
   m.attr("XENT_SLOTS") = BIGDL_XENT_SLOTS;
+  m.attr("LARS_CHUNK") = BIGDL_LARS_CHUNK;
+  m.attr("LARS_BLOCK_CAP") = BIGDL_LARS_BLOCK_CAP;
   m.def("bn_bwd_reduce", &bn_bwd_reduce, py::arg("dz"), py::arg("z"), py::arg("x"), py::arg("mean"), py::arg("red"),
         py::arg("P"), py::arg("C"), py::arg("aff") = py::none(), py::arg("zm") = py::none());
   m.def("bn_bwd_apply", &bn_bwd_apply, py::arg("dz"), py::arg("z"), py::arg("x"), py::arg("mean"), py::arg("invstd"),
@@ -2155,6 +2204,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sgd_step", &sgd_step, py::arg("w"), py::arg("g"), py::arg("mom"), py::arg("w16"), py::arg("lr"), py::arg("wd"), py::arg("momentum"), py::arg("dampening"), py::arg("nesterov"), py::arg("first"), py::arg("lr_dev") = py::none(), py::arg("seg_off") = py::none(), py::arg("seg_wd") = py::none(), py::arg("base") = 0);
   m.def("adam_step", &adam_step);
   m.def("optim_step", &optim_step);
+  m.def("lars_norms", &lars_norms, py::arg("w"), py::arg("g"), py::arg("chunk_piece"), py::arg("chunk_start"), py::arg("piece_tab"), py::arg("layer_chunks"), py::arg("ws"), py::arg("acc"), py::arg("max_hi"));
+  m.def("lars_update", &lars_update, py::arg("w"), py::arg("g"), py::arg("v"), py::arg("w16"), py::arg("chunk_piece"), py::arg("chunk_start"), py::arg("piece_tab"), py::arg("piece_hp"), py::arg("rates"), py::arg("acc"), py::arg("WD"), py::arg("max_hi"), py::arg("v_need"), py::arg("nlayers"));
   m.def("sumsq", &sumsq, py::arg("x"), py::arg("out"), py::arg("workspace") = true);
   m.def("scale_f32", &scale_f32);
   m.def("lstm_cell_fwd", &lstm_cell_fwd);

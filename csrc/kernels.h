@@ -663,6 +663,25 @@ typedef struct { float a, b, c, d, e, om; } OptimHP;
 int bigdl_optim_step(int method, const OptimHP* hp, float* x, const float* g, float* s1, float* s2, uint16_t* w16,
                      long n, hipStream_t st);
 
+// Fused LARS over every layer at once (csrc/lars.hip). A *piece* is [lo, hi) of the flat fp32 buffers and belongs to
+// one layer; a *chunk* is up to BIGDL_LARS_CHUNK consecutive elements of one piece. Tables (device memory):
+// chunk_piece int32 [nchunks], chunk_start int64 [nchunks] (absolute element index), piece_tab int64 [npieces][4] =
+// (lo, hi, momentum offset - lo, layer), piece_hp fp32 [npieces][2] = (weight decay, momentum), layer_chunks int32
+// [nlayers][2] = [first chunk, end chunk). w, g, v (and w16) must share one 16-byte phase: (address / element size)
+// mod 4 is the same for all of them (-1 otherwise), so that one head / 16-byte body / tail split serves them all.
+// bigdl_lars_norms: ws[2 c], ws[2 c + 1] = sum w^2, sum g^2 of chunk c (plain stores), then acc[2 l], acc[2 l + 1] =
+// the sums of layer l's chunks in a fixed order (0 for a layer without a chunk): two launches, no atomics.
+// bigdl_lars_update: scale = guard((sqrt(acc g) + WD sqrt(acc w)) / sqrt(acc w)), rate = rates[piece] / scale,
+// v = momentum v + (g + wd w) rate, w -= v, w16 = bf16(w) (w16 optional): one launch.
+#define BIGDL_LARS_CHUNK 4096
+#define BIGDL_LARS_BLOCK_CAP 2048
+int bigdl_lars_norms(const float* w, const float* g, const int* chunk_piece, const long* chunk_start,
+                     const long* piece_tab, const int* layer_chunks, float* ws, float* acc, int nchunks, int nlayers,
+                     hipStream_t st);
+int bigdl_lars_update(float* w, const float* g, float* v, uint16_t* w16, const int* chunk_piece,
+                      const long* chunk_start, const long* piece_tab, const float* piece_hp, const float* rates,
+                      const float* acc, double WD, int nchunks, hipStream_t st);
+
 // Point-wise activations (csrc/activation.hip): kind codes in bigdl_amd/nn/activation.py _NATIVE_KIND; x, y, dy, dx
 // are contiguous bf16 (bf16 = 1) or fp32 buffers of n elements; returns -1 for an unknown kind.
 int bigdl_act_fwd(const void* x, void* y, long n, int bf16, int kind, float a, float b, hipStream_t st);
