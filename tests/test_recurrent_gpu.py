@@ -1,11 +1,19 @@
 """Recurrent layers on the GPU engine: MFMA Linear input projection (bf16) + fused HIP LSTM cell kernels vs
 the fp32 CPU engine."""
 import copy
+import os
+import sys
 
 import pytest
 import time
 
 import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from tests.recurrent_cases import _keep_mask, _philox_np  # noqa: E402,F401  (the Philox oracle lives with the cases)
 
 pytestmark = pytest.mark.gpu
 
@@ -346,34 +354,6 @@ def test_persistent_gru_sequence_matches_step_kernels(B, T, H):
         outs.append(h)
     ref = torch.stack(outs, 1)
     assert _rel(res[1][0], ref) < 1e-2
-
-
-def _philox_np(seed, ctr):
-    """Philox-4x32-10 (csrc/lstm_drop.hip philox4) over a numpy array of 64-bit counters -> 4 uint32 arrays."""
-    import numpy as np
-
-    M = np.uint64(0xFFFFFFFF)
-    ctr = ctr.astype(np.uint64)
-    c0, c1 = ctr & M, ctr >> np.uint64(32)
-    c2 = np.zeros_like(c0)
-    c3 = np.zeros_like(c0)
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        n0 = (p1 >> np.uint64(32)) ^ c1 ^ k0
-        n2 = (p0 >> np.uint64(32)) ^ c3 ^ k1
-        c1, c3, c0, c2 = p1 & M, p0 & M, n0 & M, n2 & M
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
-    return c0, c1, c2, c3
-
-
-def _keep_mask(seed, ids, p):
-    import numpy as np
-
-    r = _philox_np(seed, ids >> 2)
-    sel = np.choose((ids & 3).astype(np.int64), r)
-    return ((sel >> np.uint64(8)).astype(np.float64) / 16777216.0) >= p
 
 
 @pytest.mark.parametrize("B,T,I,H,p", [(5, 4, 12, 32, 0.3), (16, 6, 40, 64, 0.5)])
