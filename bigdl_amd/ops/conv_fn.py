@@ -8,11 +8,20 @@ bf16 NHWC with channels zero-padded to multiples of 8 (the kernels' 16-byte gran
 
     conv2d(x, w, b, stride, pad, dil)           y = x (*) w        fwd: NT GEMM, bwd: dgrad + wgrad kernels
     conv_transpose2d(x, w, b, stride, pad, adj) y = x (*)^T w      fwd: the dgrad kernel, bwd: fwd + wgrad
-    conv3d(x, w, b, stride, pad)                sum over the kT taps of 2-D convs on depth-gathered batches
+    conv3d(x, w, b, stride, pad)                native 3-D implicit GEMM (csrc/conv3d.hip), one launch per direction
+    conv_transpose3d(x, w, b, stride, pad, adj) fwd: the 3-D dgrad kernel, bwd: 3-D fwd + wgrad
+
+The 3-D functions run bf16 NDHWC operands with fp32 results (every tap accumulated in fp32, nothing rounded to bf16
+afterwards); the weight gradient's voxel splits are summed in fixed order, so it is deterministic.
+BIGDL_CONV3D_NATIVE=0 (read at import) selects the older path instead: one 2-D convolution per temporal tap on
+depth-gathered batches, which also serves geometries the 3-D kernels do not take (pad >= kernel extent).
 
 Reference: S/nn/SpatialConvolution.scala, SpatialFullConvolution.scala:71, TemporalConvolution.scala,
 SpatialConvolutionMap.scala, SpatialSeparableConvolution.scala:54, VolumetricConvolution.scala:51.
 """
+import math
+import os
+
 import torch
 import torch.nn.functional as F
 
@@ -211,12 +220,174 @@ def conv1d(x, w, b=None, stride=1):
     return conv2d(x.unsqueeze(2), w.unsqueeze(2), b, (1, stride), (0, 0)).squeeze(2)
 
 
+def _ndhwc16(x, C8):
+    """fp32/bf16 NCDHW -> contiguous bf16 [N][T][H][W][C8] (channels zero-padded) in one copy."""
+    N, C, T, H, W = x.shape
+    y = torch.empty(N, T, H, W, C8, dtype=BF16, device=x.device)
+    y[..., :C].copy_(x.permute(0, 2, 3, 4, 1))
+    if C8 != C:
+        y[..., C:].zero_()
+    return y
+
+
+def _w3d16(w, K8, C8):
+    """(K, C, kT, kH, kW) -> contiguous bf16 [K8][kT][kH][kW][C8], zero-padded."""
+    K, C = w.shape[0], w.shape[1]
+    y = _zeros(K8, *w.shape[2:], C8, dtype=BF16, device=w.device)
+    y[:K, ..., :C].copy_(w.permute(0, 2, 3, 4, 1))
+    return y
+
+
+def _ncdhw(y, C):
+    """fp32 [N][T][H][W][C8] -> contiguous NCDHW over the first C channels."""
+    return y[..., :C].permute(0, 4, 1, 2, 3).contiguous()
+
+
+def _pad_bias(b, K, K8):
+    if b is None:
+        return None
+    return b.float().contiguous() if K8 == K else F.pad(b.float(), (0, K8 - K))
+
+
+def _wgrad3d(dy16, x16, wshape, geo, want_db):
+    """dw [K8][kT][kH][kW][C8] (and db [K8]) of the convolution x16 -> dy16's grid: one launch plus the fixed-order
+    sum of its voxel splits."""
+    from . import native
+
+    C = native.get()
+    dw = _zeros(wshape, device=dy16.device)
+    db = _zeros(wshape[0], device=dy16.device) if want_db else None
+    splits = C.conv3d_wgrad_splits(dy16, x16, dw, geo)
+    ws = torch.empty(splits * (dw.numel() + wshape[0]), dtype=torch.float32, device=dy16.device)
+    C.conv3d_wgrad(dy16, x16, dw, db, ws, geo)
+    return dw, db
+
+
+class _Conv3d(torch.autograd.Function):
+    """Volumetric convolution on csrc/conv3d.hip: one launch per direction, fp32 results."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, pad):
+        from . import native
+
+        K, C = w.shape[0], w.shape[1]
+        K8, C8 = _p8(K), _p8(C)
+        N, _, T, H, W = x.shape
+        OT, OH, OW = (_out_size(e, k, s, p, 1) for e, k, s, p in zip((T, H, W), w.shape[2:], stride, pad))
+        x16, w16 = _ndhwc16(x, C8), _w3d16(w, K8, C8)
+        geo = list(stride) + list(pad)
+        y = torch.empty(N, OT, OH, OW, K8, dtype=torch.float32, device=x.device)
+        native.get().conv3d_fwd(x16, w16, _pad_bias(b, K, K8), y, geo)
+        ctx.save_for_backward(x16, w16)
+        ctx.geo = (geo, K, C, b is not None)
+        return _ncdhw(y, K)
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import native
+
+        x16, w16 = ctx.saved_tensors
+        geo, K, C, has_b = ctx.geo
+        gy16 = _ndhwc16(gy, w16.shape[0])
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gi = torch.empty(x16.shape, dtype=torch.float32, device=gy.device)
+            native.get().conv3d_dgrad(gy16, w16.permute(4, 1, 2, 3, 0).contiguous(), None, gi, geo)
+            gx = _ncdhw(gi, C)
+        if ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2]):
+            dw, db = _wgrad3d(gy16, x16, w16.shape, geo, has_b)
+            gw = dw[:K, ..., :C].permute(0, 4, 1, 2, 3).contiguous()
+            gb = db[:K] if has_b else None
+        return gx, gw, gb, None, None
+
+
+class _ConvT3d(torch.autograd.Function):
+    """y = conv_transpose3d(x, w): the data gradient of the convolution that maps y's grid to x's with weight w
+    (w: [Cin, Cout, kT, kH, kW] is that convolution's [K, C, kT, kH, kW]); the bias is added in the kernel."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, pad, adj):
+        from . import native
+
+        Cin, Cout = w.shape[0], w.shape[1]
+        K8, C8 = _p8(Cin), _p8(Cout)
+        N = x.shape[0]
+        OT, OH, OW = ((e - 1) * s - 2 * p + k + a for e, k, s, p, a in zip(x.shape[2:], w.shape[2:], stride, pad, adj))
+        x16, w16 = _ndhwc16(x, K8), _w3d16(w, K8, C8)
+        geo = list(stride) + list(pad)
+        y = torch.empty(N, OT, OH, OW, C8, dtype=torch.float32, device=x.device)
+        native.get().conv3d_dgrad(x16, w16.permute(4, 1, 2, 3, 0).contiguous(), _pad_bias(b, Cout, C8), y, geo)
+        ctx.save_for_backward(x16, w16)
+        ctx.geo = (geo, Cin, Cout, b is not None)
+        return _ncdhw(y, Cout)
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import native
+
+        x16, w16 = ctx.saved_tensors
+        geo, Cin, Cout, has_b = ctx.geo
+        gy16 = _ndhwc16(gy, w16.shape[4])
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            # the forward of the underlying convolution (input = gy, output grid = x's)
+            gi = torch.empty(x16.shape, dtype=torch.float32, device=gy.device)
+            native.get().conv3d_fwd(gy16, w16, None, gi, geo)
+            gx = _ncdhw(gi, Cin)
+        if ctx.needs_input_grad[1]:
+            dw, _ = _wgrad3d(x16, gy16, w16.shape, geo, False)
+            gw = dw[:Cin, ..., :Cout].permute(0, 4, 1, 2, 3).contiguous()
+        if has_b and ctx.needs_input_grad[2]:
+            gb = gy.sum(dim=(0, 2, 3, 4))
+        return gx, gw, gb, None, None, None
+
+
+# BIGDL_CONV3D_NATIVE=0 keeps 3-D convolution on the per-temporal-tap 2-D path below
+CONV3D_NATIVE = [os.environ.get("BIGDL_CONV3D_NATIVE", "1") != "0"]
+
+
+def _native3d(x, w, stride, pad, adj=None):
+    """What csrc/conv3d.hip takes (its geo_ok): strides >= 1, 0 <= pad < kernel extent, adj < stride, no empty
+    extent on either grid, and fewer than 2^31 elements in each padded operand. adj is given for the transposed
+    convolution, whose x lives on the underlying convolution's output grid."""
+    k = w.shape[2:]
+    if not (CONV3D_NATIVE[0] and all(s >= 1 for s in stride) and all(0 <= p < e for p, e in zip(pad, k))):
+        return False
+    if adj is None:
+        other = [_out_size(e, kk, s, p, 1) for e, kk, s, p in zip(x.shape[2:], k, stride, pad)]
+    elif all(0 <= a < s for a, s in zip(adj, stride)):
+        other = [(e - 1) * s - 2 * p + kk + a for e, kk, s, p, a in zip(x.shape[2:], k, stride, pad, adj)]
+    else:
+        return False
+    if min(x.shape) < 1 or min(w.shape) < 1 or min(other) < 1 or math.prod(stride) > 65535:   # phases ride grid.z
+        return False
+    c_x, c_other = (_p8(w.shape[1]), _p8(w.shape[0])) if adj is None else (_p8(w.shape[0]), _p8(w.shape[1]))
+    vox_x, vox_other, lim = x.shape[0] * math.prod(x.shape[2:]), x.shape[0] * math.prod(other), 1 << 31
+    return vox_x * c_x < lim and vox_other * c_other < lim and math.prod(k) * c_x * c_other < lim
+
+
 def conv_transpose3d(x, w, b=None, stride=(1, 1, 1), pad=(0, 0, 0), adj=(0, 0, 0)):
-    """x: [N, Cin, T, H, W], w: [Cin, Cout, kT, kH, kW]. Input frame t feeds output frames t*sT + kt - pT: each
-    temporal tap kt is a native 2-D transposed convolution of all frames (folded into the batch), scattered into
-    the output frames with index_add (the adjoint of conv3d's depth gather)."""
+    """x: [N, Cin, T, H, W], w: [Cin, Cout, kT, kH, kW]: the native data-gradient kernel run forward."""
     if not x.is_cuda:
         return F.conv_transpose3d(x, w, b, stride, pad, adj)
+    if _native3d(x, w, stride, pad, tuple(adj)):
+        return _ConvT3d.apply(x, w, b, tuple(stride), tuple(pad), tuple(adj))
+    return _conv_transpose3d_taps(x, w, b, stride, pad, adj)
+
+
+def conv3d(x, w, b=None, stride=(1, 1, 1), pad=(0, 0, 0)):
+    """x: [N, C, T, H, W], w: [K, C, kT, kH, kW]: one native launch per direction."""
+    if not x.is_cuda:
+        return F.conv3d(x, w, b, stride, pad)
+    if _native3d(x, w, stride, pad):
+        return _Conv3d.apply(x, w, b, tuple(stride), tuple(pad))
+    return _conv3d_taps(x, w, b, stride, pad)
+
+
+def _conv_transpose3d_taps(x, w, b, stride, pad, adj):
+    """Per-tap alternative: input frame t feeds output frames t*sT + kt - pT, so each temporal tap kt is a native 2-D
+    transposed convolution of all frames (folded into the batch), scattered into the output frames with index_add
+    (the adjoint of _conv3d_taps' depth gather)."""
     N, Cin, T, H, W = x.shape
     _, Cout, kT, kH, kW = w.shape
     sT, sH, sW = stride
@@ -238,11 +409,9 @@ def conv_transpose3d(x, w, b=None, stride=(1, 1, 1), pad=(0, 0, 0), adj=(0, 0, 0
     return y.contiguous()
 
 
-def conv3d(x, w, b=None, stride=(1, 1, 1), pad=(0, 0, 0)):
-    """x: [N, C, T, H, W], w: [K, C, kT, kH, kW]. Each temporal tap kt is a 2-D convolution of the depth slices
-    t*sT + kt - pT (zero outside) folded into the batch; the kT partial outputs are summed."""
-    if not x.is_cuda:
-        return F.conv3d(x, w, b, stride, pad)
+def _conv3d_taps(x, w, b, stride, pad):
+    """Per-tap alternative: each temporal tap kt is a 2-D convolution of the depth slices t*sT + kt - pT (zero
+    outside) folded into the batch; the kT partial outputs are summed."""
     N, C, T, H, W = x.shape
     K, _, kT, kH, kW = w.shape
     sT, sH, sW = stride

@@ -2054,6 +2054,59 @@ void gconv(int64_t pass, const Tensor& x_or_dx, const Tensor& w_or_dw, const Opt
   else { c.x = cf(x, "x"); c.dwt = mf(w, "dw"); c.db = omf(b_or_db, "db"); c.dy = cf(y, "dy"); }
   TORCH_CHECK(bigdl_gconv(&c, (int)pass, stream()) == 0, "gconv: bad geometry");
 }
+// Volumetric convolution (csrc/conv3d.hip). x [N][T][H][W][C] and y [N][OT][OH][OW][K] are contiguous NDHWC tensors
+// of the convolution's input and output grids (bf16 as operands, fp32 as results), w is [K][kT][kH][kW][C] or, for the
+// data gradient, wt [C][kT][kH][kW][K]; geo = [sT, sH, sW, pT, pH, pW]. Every extent is read from the tensors, so
+// the kernels' bounds are the tensors' own.
+static Conv3dArgs conv3d_args(const Tensor& x, const Tensor& y, at::IntArrayRef k, const std::vector<int64_t>& geo) {
+  TORCH_CHECK(x.dim() == 5 && y.dim() == 5 && x.is_contiguous() && y.is_contiguous() && x.size(0) == y.size(0),
+              "conv3d: x / y must be contiguous [N][T][H][W][C] tensors of one batch");
+  TORCH_CHECK(geo.size() == 6, "conv3d: geo = [sT, sH, sW, pT, pH, pW]");
+  for (int i = 0; i < 5; ++i) TORCH_CHECK(x.size(i) < (1ll << 31) && y.size(i) < (1ll << 31), "conv3d: extent out of range");
+  for (int i = 0; i < 6; ++i) TORCH_CHECK(geo[i] >= 0 && geo[i] < (1 << 20), "conv3d: stride / pad out of range");
+  Conv3dArgs g;
+  g.N = (int)x.size(0); g.T = (int)x.size(1); g.H = (int)x.size(2); g.W = (int)x.size(3); g.C = (int)x.size(4);
+  g.OT = (int)y.size(1); g.OH = (int)y.size(2); g.OW = (int)y.size(3); g.K = (int)y.size(4);
+  g.kT = (int)k[0]; g.kH = (int)k[1]; g.kW = (int)k[2];
+  g.sT = (int)geo[0]; g.sH = (int)geo[1]; g.sW = (int)geo[2]; g.pT = (int)geo[3]; g.pH = (int)geo[4]; g.pW = (int)geo[5];
+  return g;
+}
+static void conv3d_w_check(const Tensor& w, int64_t rows, int64_t cols, const char* what) {
+  TORCH_CHECK(w.dim() == 5 && w.is_contiguous() && w.size(0) == rows && w.size(4) == cols, what);
+}
+void conv3d_fwd(const Tensor& x, const Tensor& w, const OptT& bias, const Tensor& y, std::vector<int64_t> geo) {
+  conv3d_w_check(w, y.dim() == 5 ? y.size(4) : -1, x.dim() == 5 ? x.size(4) : -1, "conv3d_fwd: w must be [K][kT][kH][kW][C]");
+  const Conv3dArgs g = conv3d_args(x, y, w.sizes().slice(1, 3), geo);
+  if (bias && bias->defined()) TORCH_CHECK(bias->numel() == g.K && bias->is_contiguous(), "conv3d_fwd: bias is [K]");
+  TORCH_CHECK(bigdl_conv3d_fwd(cbf(x, "x"), cbf(w, "w"), ocf(bias, "bias"), mf(y, "y"), &g, stream()) == 0,
+              "conv3d_fwd: unsupported geometry");
+}
+void conv3d_dgrad(const Tensor& dy, const Tensor& wt, const OptT& bias, const Tensor& dx, std::vector<int64_t> geo) {
+  conv3d_w_check(wt, dx.dim() == 5 ? dx.size(4) : -1, dy.dim() == 5 ? dy.size(4) : -1,
+                 "conv3d_dgrad: wt must be [C][kT][kH][kW][K]");
+  const Conv3dArgs g = conv3d_args(dx, dy, wt.sizes().slice(1, 3), geo);
+  if (bias && bias->defined()) TORCH_CHECK(bias->numel() == g.C && bias->is_contiguous(), "conv3d_dgrad: bias is [C]");
+  TORCH_CHECK(bigdl_conv3d_dgrad(cbf(dy, "dy"), cbf(wt, "wt"), ocf(bias, "bias"), mf(dx, "dx"), &g, stream()) == 0,
+              "conv3d_dgrad: unsupported geometry");
+}
+// number of voxel splits conv3d_wgrad takes for these tensors (the workspace is splits * (dw.numel() + K) floats)
+int64_t conv3d_wgrad_splits(const Tensor& dy, const Tensor& x, const Tensor& dw, std::vector<int64_t> geo) {
+  conv3d_w_check(dw, dy.dim() == 5 ? dy.size(4) : -1, x.dim() == 5 ? x.size(4) : -1, "conv3d_wgrad: dw must be [K][kT][kH][kW][C]");
+  const Conv3dArgs g = conv3d_args(x, dy, dw.sizes().slice(1, 3), geo);
+  const int n = bigdl_conv3d_wgrad_splits(&g);
+  TORCH_CHECK(n > 0, "conv3d_wgrad: unsupported geometry");
+  return n;
+}
+int64_t conv3d_wgrad_split_min() { return bigdl_conv3d_wgrad_split_min(); }
+void conv3d_wgrad(const Tensor& dy, const Tensor& x, const Tensor& dw, const OptT& db, const Tensor& ws,
+                  std::vector<int64_t> geo) {
+  const int64_t splits = conv3d_wgrad_splits(dy, x, dw, geo);
+  const Conv3dArgs g = conv3d_args(x, dy, dw.sizes().slice(1, 3), geo);
+  if (db && db->defined()) TORCH_CHECK(db->numel() == g.K && db->is_contiguous(), "conv3d_wgrad: db is [K]");
+  TORCH_CHECK(ws.is_contiguous() && ws.numel() >= splits * (dw.numel() + g.K), "conv3d_wgrad: workspace too small");
+  TORCH_CHECK(bigdl_conv3d_wgrad(cbf(dy, "dy"), cbf(x, "x"), mf(dw, "dw"), omf(db, "db"), mf(ws, "ws"), &g, stream()) == 0,
+              "conv3d_wgrad: unsupported geometry");
+}
 void ones_col_pack(const Tensor& x, const Tensor& xe) {
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && x.size(1) % 8 == 0, "ones_col_pack: x must be [M, K] contiguous, K % 8 == 0");
   TORCH_CHECK(xe.dim() == 2 && xe.is_contiguous() && xe.size(0) == x.size(0) && xe.size(1) == x.size(1) + 8,
@@ -2290,6 +2343,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"), py::arg("H"),
         py::arg("causal"), py::arg("o"), py::arg("lse"), py::arg("mlog"), py::arg("drop_p") = 0.0, py::arg("seed") = 0);
   m.def("gconv", &gconv);
+  m.def("conv3d_fwd", &conv3d_fwd);
+  m.def("conv3d_dgrad", &conv3d_dgrad);
+  m.def("conv3d_wgrad", &conv3d_wgrad);
+  m.def("conv3d_wgrad_splits", &conv3d_wgrad_splits);
+  m.def("conv3d_wgrad_split_min", &conv3d_wgrad_split_min);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("kcache"), py::arg("vcache"), py::arg("length"),
         py::arg("heads"), py::arg("rows"), py::arg("bias"), py::arg("o"));
   m.def("kv_append", &kv_append);

@@ -728,4 +728,21 @@ typedef struct {
 } GemmBf16Args;
 size_t bigdl_gemm_bf16_ws_bytes(int form, int M, int N, int K);
 int bigdl_gemm_bf16(const GemmBf16Args* a, size_t ws_bytes, hipStream_t st);
+
+// Volumetric convolution (csrc/conv3d.hip). The geometry is that of the convolution x[N][T][H][W][C] (*) w -> y[N][OT]
+// [OH][OW][K] whichever direction runs: bf16 NDHWC activations, C and K multiples of 8, 0 <= pad < kernel extent.
+typedef struct { int N, T, H, W, C, OT, OH, OW, K, kT, kH, kW, sT, sH, sW, pT, pH, pW; } Conv3dArgs;
+// y = x (*) w + bias: w bf16 [K][kT][kH][kW][C], y fp32 [N][OT][OH][OW][K]
+int bigdl_conv3d_fwd(const uint16_t* x, const uint16_t* w, const float* bias, float* y, const Conv3dArgs* g,
+                     hipStream_t st);
+// dx = dy (*)^T w + bias (every element of dx is written): wt bf16 [C][kT][kH][kW][K], dx fp32 [N][T][H][W][C]
+int bigdl_conv3d_dgrad(const uint16_t* dy, const uint16_t* wt, const float* bias, float* dx, const Conv3dArgs* g,
+                       hipStream_t st);
+// dw[K][kT][kH][kW][C] += dy^T x, db[K] += column sums of dy (db may be null). ws: fp32 workspace of
+// bigdl_conv3d_wgrad_splits(g) * (K * taps * C + K) floats. The voxels are split once there are at least
+// bigdl_conv3d_wgrad_split_min() of them and the tiles alone leave the chip short; splits are summed in fixed order.
+int bigdl_conv3d_wgrad_splits(const Conv3dArgs* g);
+int bigdl_conv3d_wgrad_split_min(void);
+int bigdl_conv3d_wgrad(const uint16_t* dy, const uint16_t* x, float* dw, float* db, float* ws, const Conv3dArgs* g,
+                       hipStream_t st);
 }
