@@ -19,7 +19,9 @@ loop entirely: a sequence-level autograd Function runs ``h @ U^T`` (library GEMM
 the gradient of both in one pass) per step, and computes dU with ONE [4H, T*B] x [T*B, H] GEMM after the
 reverse sweep instead of T small ones. LSTMPeephole (p == 0) and the maskZero LSTM take the same shape of path on
 the GPU (``_LSTMPeepSeq``: csrc/lstm.hip, one fused launch per step with peephole terms and a row mask in
-the cell epilogue); every other masked cell runs the generic loop.
+the cell epilogue); every other masked cell runs the generic loop. The 2-D ConvLSTMPeephole (stride 1, "same"
+padding, outputSize % 16 == 0) runs ``_ConvLSTMSeq``: csrc/convlstm.hip, one fused halo-convolution + cell launch per
+step and direction, every other convolution once per sequence.
 """
 import os
 
@@ -34,7 +36,7 @@ __all__ = ["Cell", "RnnCell", "RNN", "LSTM", "LSTMPeephole", "GRU", "ConvLSTMPee
 from .. import ops
 from ..utils.table import Table
 from .abstractnn import AbstractModule
-from .activation import CMul, Sigmoid, Tanh
+from .activation import CMul, HardSigmoid, Sigmoid, Tanh
 from .containers import Container
 from .conv import SpatialConvolution, VolumetricConvolution, _same_pad
 from .linear import Linear
@@ -1028,6 +1030,198 @@ class GRU(Cell):
         return super().sequence(x2, hid, mask)
 
 
+# BIGDL_CONVLSTM_FUSED=0 sends the 2-D ConvLSTMPeephole back to the Python time loop (Cell.sequence) (A/B)
+_CONVLSTM_FUSED = [os.environ.get("BIGDL_CONVLSTM_FUSED", "1") != "0"]
+
+
+class _ConvLSTMSeq(torch.autograd.Function):
+    """Whole-sequence 2-D ConvLSTMPeephole: x [B, T, Cin, H, W], stride 1, odd kernels with "same" zero padding, gate
+    order (i, f, g, o), tanh outside, sigmoid or hard-sigmoid (``hard``) inside, peepholes pI, pF on c_{t-1} and pO on
+    c_t (all three or None).
+
+    GPU (fp32 x, C % 16 == 0, kernelC <= 7): csrc/convlstm.hip, one fused launch per step and direction on channels-last
+    time-major buffers (bf16 h and gate gradients, fp32 projection, c, gates and output). Everything else happens once per
+    sequence on the native convolution entry points: the input projection of all T steps, dU over the stacked
+    (dg, h_{0..T-1}), dW / db over (dg, x), dx and dh_0; the peephole gradients by a fixed-order reduction. The
+    output is a channels-last-strided view of the time-major buffer.
+    Other tensors: the same forward and the same hand-derived backward in plain torch, in the tensors' own dtype (the
+    modules do not route the CPU engine here; it keeps the formulas checkable in fp64)."""
+
+    @staticmethod
+    def usable(x, cell, mask=None):
+        kI, kC, pad = cell.kernelI, cell.kernelC, cell.padding
+        return (_CONVLSTM_FUSED[0] and cell._nd == 2 and mask is None and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 5 and x.shape[1] > 0 and cell.outputSize % 16 == 0 and cell.stride == 1
+                and kC % 2 == 1 and kC <= 7 and kI % 2 == 1 and (pad == -1 or 2 * pad == kI - 1 == kC - 1)
+                and _is(cell.activation, Tanh) and (_is(cell.innerActivation, Sigmoid)
+                                                    or _is(cell.innerActivation, HardSigmoid)))
+
+    @staticmethod
+    def _inner(a, hard):
+        return torch.clamp(0.2 * a + 0.5, 0.0, 1.0) if hard else torch.sigmoid(a)
+
+    @staticmethod
+    def _inner_grad(s, hard):
+        return ((s > 0) & (s < 1)).to(s.dtype) * 0.2 if hard else s * (1 - s)
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, Wi, bi, U, pI, pF, pO, hard):
+        ctx.set_materialize_grads(False)
+        B, T, Cin, H, W = x.shape
+        C = U.shape[0] // 4
+        kI, kC = Wi.shape[2], U.shape[2]
+        peep = pI is not None
+        assert (pF is not None) == peep and (pO is not None) == peep, "peepholes: all three or none"
+        ctx.peep, ctx.hard, ctx.has_bias = peep, bool(hard), bi is not None
+        ctx.pshapes = [p.shape for p in (pI, pF, pO)] if peep else None
+        ctx.fused = x.is_cuda and x.dtype == torch.float32 and C % 16 == 0 and kC <= 7
+        if ctx.fused:
+            from ..ops import conv as cv
+
+            N = ops.native.get()
+            train = any(ctx.needs_input_grad)
+            # time-major from here on: step t is one dense [B, H, W, .] slab of every buffer
+            x16 = cv.to_nhwc_bf16(x.detach().transpose(0, 1).reshape(T * B, Cin, H, W))
+            Wi16 = cv.weight_krsc_bf16(Wi.detach())
+            U16 = cv.weight_krsc_bf16(U.detach())
+            # fp32 projection: a bf16-rounded pre-activation would move elements across the hard-sigmoid's kinks
+            xg = torch.empty((T * B, 4 * C, H, W), dtype=torch.float32, device=x.device,
+                             memory_format=torch.channels_last)
+            cv.conv2d_fwd(x16, Wi16, bi.detach().float().contiguous() if bi is not None else None, (1, 1),
+                          ((kI - 1) // 2,) * 2, out=xg)
+            xg = xg.permute(0, 2, 3, 1).view(T, B, H, W, 4 * C)
+            ps = [p.detach().reshape(C).contiguous() for p in (pI, pF, pO)] if peep else [None, None, None]
+            out = x.new_empty(T, B, H, W, C)
+            cs = x.new_empty(T, B, H, W, C)
+            acts = x.new_empty(T, B, H, W, 4 * C) if train else None
+            h16 = x.new_empty(T + 1, B, H, W, C, dtype=torch.bfloat16)
+            h16[0].copy_(h0.detach().permute(0, 2, 3, 1))
+            c0n = c0.detach().permute(0, 2, 3, 1).contiguous()
+            Uk = U16.permute(0, 2, 3, 1)                      # [4C, k, k, C]: the KRSC memory as it lies
+            for t in range(T):
+                N.convlstm_fwd_step(Uk, h16[t], xg[t], cs[t - 1] if t > 0 else c0n, cs[t], out[t], h16[t + 1],
+                                    acts[t] if train else None, pI=ps[0], pF=ps[1], pO=ps[2], hard=ctx.hard)
+            if train:
+                ctx.save_for_backward(x16, Wi16, U16, c0n, cs, acts, h16, *ps)
+                ctx.cin = Cin
+            return (out.permute(1, 0, 4, 2, 3), out[-1].permute(0, 3, 1, 2).contiguous(),
+                    cs[-1].permute(0, 3, 1, 2).contiguous())
+        inner = _ConvLSTMSeq._inner
+        xg = F.conv2d(x.reshape(B * T, Cin, H, W), Wi, bi, padding=(kI - 1) // 2).view(B, T, 4 * C, H, W)
+        h, c = h0, c0
+        hs, cs, gi, gf, gg, go = ([] for _ in range(6))
+        for t in range(T):
+            g = xg[:, t] + F.conv2d(h, U, None, padding=(kC - 1) // 2)
+            ai, af = g[:, :C], g[:, C:2 * C]
+            if peep:
+                ai, af = ai + pI * c, af + pF * c
+            i, f, gc = inner(ai, hard), inner(af, hard), torch.tanh(g[:, 2 * C:3 * C])
+            c = f * c + i * gc
+            ao = g[:, 3 * C:]
+            if peep:
+                ao = ao + pO * c
+            o = inner(ao, hard)
+            h = o * torch.tanh(c)
+            hs.append(h); cs.append(c); gi.append(i); gf.append(f); gg.append(gc); go.append(o)
+        hs, cs = torch.stack(hs), torch.stack(cs)
+        ctx.save_for_backward(x, h0, c0, Wi, U, hs, cs, torch.stack(gi), torch.stack(gf), torch.stack(gg),
+                              torch.stack(go), pI, pF, pO)
+        return hs.transpose(0, 1).contiguous(), hs[-1].clone(), cs[-1].clone()
+
+    @staticmethod
+    def _backward_fused(ctx, dout, dhT, dcT):
+        from ..ops import conv as cv
+
+        x16, Wi16, U16, c0n, cs, acts, h16, pI, pF, pO = ctx.saved_tensors
+        T, B, H, W, C = cs.shape
+        N = ops.native.get()
+        kI, kC = Wi16.shape[2], U16.shape[2]
+        padI, padC = ((kI - 1) // 2,) * 2, ((kC - 1) // 2,) * 2
+        if dout is not None:
+            dout = dout.permute(1, 0, 3, 4, 2).contiguous()        # no copy for a gradient laid out like the output
+        dhT = dhT.permute(0, 2, 3, 1).contiguous() if dhT is not None else None
+        # dc is updated in place by every step: always a private channels-last copy of the incoming gradient
+        dc = dcT.permute(0, 2, 3, 1).clone(memory_format=torch.contiguous_format) if dcT is not None \
+            else ops.zeros(B, H, W, C, device=cs.device)
+        UT16 = cv.transpose_w(U16)                                 # [C, k, k, 4C]
+        dg16 = cs.new_empty(T, B, H, W, 4 * C, dtype=torch.bfloat16)
+        for t in range(T - 1, -1, -1):
+            N.convlstm_bwd_step(UT16, dg16[t + 1] if t < T - 1 else None, dout[t] if dout is not None else None,
+                                dhT if t == T - 1 else None, acts[t], cs[t - 1] if t > 0 else c0n, cs[t], dc, dg16[t],
+                                pI=pI, pF=pF, pO=pO, hard=ctx.hard)
+        dg = dg16.view(T * B, H, W, 4 * C).permute(0, 3, 1, 2)      # NHWC gate gradients of all steps
+        need = ctx.needs_input_grad                                 # x, h0, c0, Wi, bi, U, pI, pF, pO
+        dh0 = dU = dWi = db = None
+        if need[1]:
+            dh0 = torch.empty((B, C, H, W), dtype=torch.float32, device=cs.device, memory_format=torch.channels_last)
+            cv.conv2d_dgrad(dg16[0].permute(0, 3, 1, 2), UT16, (B, C, H, W), (1, 1), padC, out=dh0)
+        if need[5]:
+            dU = ops.zeros(U16.shape, device=cs.device, memory_format=torch.channels_last)
+            cv.conv2d_wgrad(dg, h16[:T].view(T * B, H, W, C).permute(0, 3, 1, 2), dU, None, (1, 1), padC)
+        if need[3] or (ctx.has_bias and need[4]):
+            dWi = ops.zeros(Wi16.shape, device=cs.device, memory_format=torch.channels_last)
+            db = ops.zeros(4 * C, device=cs.device) if ctx.has_bias else None
+            cv.conv2d_wgrad(dg, x16, dWi, db, (1, 1), padI)
+            dWi = dWi[:, :ctx.cin]
+        dx = None
+        if ctx.needs_input_grad[0]:
+            Cp = x16.shape[1]
+            dx = torch.empty((T * B, Cp, H, W), dtype=torch.float32, device=cs.device,
+                             memory_format=torch.channels_last)
+            cv.conv2d_dgrad(dg, cv.transpose_w(Wi16), (T * B, Cp, H, W), (1, 1), padI, out=dx)
+            dx = dx.permute(0, 2, 3, 1).view(T, B, H, W, Cp).permute(1, 0, 4, 2, 3)[:, :, :ctx.cin]
+        dps = [None, None, None]
+        if ctx.peep and any(need[6:9]):
+            P = B * H * W
+            part = cs.new_empty(N.convlstm_peep_wgrad_slices(T * P), 3, C)
+            dp = cs.new_empty(3, C)
+            N.convlstm_peep_wgrad(dg16.view(T, P, 4 * C), cs.view(T, P, C), c0n.view(P, C), part, dp)
+            dps = [dp[k].reshape(s) for k, s in enumerate(ctx.pshapes)]
+        return (dx, dh0, dc.permute(0, 3, 1, 2), dWi, db, dU, *dps, None)
+
+    @staticmethod
+    def backward(ctx, dout, dhT, dcT):
+        if ctx.fused:
+            return _ConvLSTMSeq._backward_fused(ctx, dout, dhT, dcT)
+        x, h0, c0, Wi, U, hs, cs, gi, gf, gg, go, pI, pF, pO = ctx.saved_tensors
+        T, B, C, H, W = hs.shape
+        peep, hard = ctx.peep, ctx.hard
+        igrad = _ConvLSTMSeq._inner_grad
+        padI, padC = (Wi.shape[2] - 1) // 2, (U.shape[2] - 1) // 2
+        dh_rec = dhT if dhT is not None else torch.zeros_like(h0)
+        dc = dcT if dcT is not None else torch.zeros_like(c0)
+        dgs = hs.new_zeros(T, B, 4 * C, H, W)
+        dps = [torch.zeros_like(pI), torch.zeros_like(pF), torch.zeros_like(pO)] if peep else [None, None, None]
+        for t in range(T - 1, -1, -1):
+            c_prev = cs[t - 1] if t > 0 else c0
+            i, f, gc, o, c = gi[t], gf[t], gg[t], go[t], cs[t]
+            dh = dh_rec + dout[:, t] if dout is not None else dh_rec
+            tc = torch.tanh(c)
+            do_ = dh * tc * igrad(o, hard)
+            dcv = dh * o * (1 - tc * tc) + dc
+            if peep:
+                dcv = dcv + do_ * pO
+            di_ = dcv * gc * igrad(i, hard)
+            df_ = dcv * c_prev * igrad(f, hard)
+            dg_ = dcv * i * (1 - gc * gc)
+            dc = dcv * f
+            if peep:
+                dc = dc + di_ * pI + df_ * pF
+                dps[0] = dps[0] + (di_ * c_prev).sum((0, 2, 3)).reshape(pI.shape)
+                dps[1] = dps[1] + (df_ * c_prev).sum((0, 2, 3)).reshape(pF.shape)
+                dps[2] = dps[2] + (do_ * c).sum((0, 2, 3)).reshape(pO.shape)
+            dgs[t] = torch.cat([di_, df_, dg_, do_], 1)
+            dh_rec = torch.nn.grad.conv2d_input(h0.shape, U, dgs[t], padding=padC)
+        hprev = torch.cat([h0.unsqueeze(0), hs[:-1]], 0).reshape(T * B, C, H, W)
+        dU = torch.nn.grad.conv2d_weight(hprev, U.shape, dgs.reshape(T * B, 4 * C, H, W), padding=padC)
+        dgb = dgs.transpose(0, 1).reshape(B * x.shape[1], 4 * C, H, W)          # batch-major like x
+        xf = x.reshape(dgb.shape[0], x.shape[2], H, W)
+        dWi = torch.nn.grad.conv2d_weight(xf, Wi.shape, dgb, padding=padI)
+        db = dgb.sum((0, 2, 3)) if ctx.has_bias else None
+        dx = torch.nn.grad.conv2d_input(xf.shape, Wi, dgb, padding=padI).view(x.shape)
+        return (dx, dh_rec, dc, dWi, db, dU, *dps, None)
+
+
 class _ConvLSTMBase(Cell):
     _nd = 2
 
@@ -1100,6 +1294,15 @@ class _ConvLSTMBase(Cell):
             go = go + self.peepO.weight * c2
         h2 = sig(go) * act(c2)
         return h2, [h2, c2]
+
+    def sequence(self, x2, hid, mask=None):
+        if _ConvLSTMSeq.usable(x2, self, mask):
+            # GPU, 2-D: one fused step kernel per time step and direction (csrc/convlstm.hip)
+            peep = [self.peepI.weight, self.peepF.weight, self.peepO.weight] if self.withPeephole else [None] * 3
+            out, h, c = _ConvLSTMSeq.apply(x2, hid[0], hid[1], self.i2g.weight, self.i2g.bias, self.h2g.weight, *peep,
+                                           _is(self.innerActivation, HardSigmoid))
+            return out, [h, c]
+        return super().sequence(x2, hid, mask)
 
 
 class ConvLSTMPeephole(_ConvLSTMBase):

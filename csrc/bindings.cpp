@@ -1787,6 +1787,92 @@ void lstm_peep_wgrad(const Tensor& dg, const Tensor& cs, const OptT& c0, const T
   TORCH_CHECK(rc == 0, "lstm_peep_wgrad: unsupported arguments");
 }
 
+// Fused ConvLSTMPeephole steps (csrc/convlstm.hip). Every activation is channels-last and dense: [B, H, W, C] or
+// [B, H, W, 4C] (gate blocks i, f, g, o), 16-byte aligned; C % 16 == 0, odd kernel extent k <= 7, "same" padding.
+struct ConvLstmShape { int64_t B, H, W, C, k; };
+void convlstm_dense(const char* fn, const Tensor& t, const ConvLstmShape& s, int64_t ch, const char* name) {
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == s.B && t.size(1) == s.H && t.size(2) == s.W && t.size(3) == ch &&
+                  t.is_contiguous() && (uintptr_t)t.data_ptr() % 16 == 0,
+              fn, ": ", name, " must be a dense 16-byte aligned [B, H, W, ", ch, "] tensor");
+}
+void convlstm_opt(const char* fn, const OptT& t, const ConvLstmShape& s, int64_t ch, const char* name) {
+  if (t && t->defined()) convlstm_dense(fn, *t, s, ch, name);
+}
+struct ConvLstmPeep { const float *pI = nullptr, *pF = nullptr, *pO = nullptr; };
+ConvLstmPeep convlstm_peep(const char* fn, const OptT& pI, const OptT& pF, const OptT& pO, int64_t C) {
+  ConvLstmPeep a;
+  const bool hi = pI && pI->defined(), hf = pF && pF->defined(), ho = pO && pO->defined();
+  TORCH_CHECK(hi == hf && hi == ho, fn, ": peepholes pI, pF, pO must be given all three or not at all");
+  if (hi) {
+    for (const Tensor* p : {&*pI, &*pF, &*pO})
+      TORCH_CHECK(p->numel() == C && p->is_contiguous() && (uintptr_t)p->data_ptr() % 16 == 0, fn,
+                  ": peepholes must be [C] contiguous, 16-byte aligned");
+    a.pI = cf(*pI, "pI"); a.pF = cf(*pF, "pF"); a.pO = cf(*pO, "pO");
+  }
+  return a;
+}
+// U16: [4C, k, k, C] (the KRSC recurrent weight); h16 = h_{t-1}; xg = this step's fp32 input projection with its bias.
+void convlstm_fwd_step(const Tensor& U16, const Tensor& h16, const Tensor& xg, const Tensor& c_prev, const Tensor& c_out,
+                       const Tensor& h_out, const Tensor& h16_out, const OptT& acts, const OptT& pI, const OptT& pF,
+                       const OptT& pO, bool hard) {
+  const char* fn = "convlstm_fwd_step";
+  TORCH_CHECK(U16.dim() == 4 && U16.is_contiguous() && U16.size(1) == U16.size(2) && U16.size(0) == 4 * U16.size(3) &&
+                  (uintptr_t)U16.data_ptr() % 16 == 0, fn, ": U16 must be [4C, k, k, C] contiguous");
+  TORCH_CHECK(h16.dim() == 4, fn, ": h16 must be [B, H, W, C]");
+  const ConvLstmShape s{h16.size(0), h16.size(1), h16.size(2), U16.size(3), U16.size(1)};
+  convlstm_dense(fn, h16, s, s.C, "h16"); convlstm_dense(fn, xg, s, 4 * s.C, "xg");
+  convlstm_dense(fn, c_prev, s, s.C, "c_prev"); convlstm_dense(fn, c_out, s, s.C, "c_out");
+  convlstm_dense(fn, h_out, s, s.C, "h_out"); convlstm_dense(fn, h16_out, s, s.C, "h16_out");
+  convlstm_opt(fn, acts, s, 4 * s.C, "acts");
+  TORCH_CHECK(h16_out.data_ptr() != h16.data_ptr(), fn, ": h16_out must not alias h16 (neighbouring tiles read it)");
+  const ConvLstmPeep p = convlstm_peep(fn, pI, pF, pO, s.C);
+  const int rc = bigdl_convlstm_fwd_step(cbf(U16, "U16"), cbf(h16, "h16"), cf(xg, "xg"), cf(c_prev, "c_prev"),
+                                         mf(c_out, "c_out"), mbf(h16_out, "h16_out"), mf(h_out, "h_out"),
+                                         omf(acts, "acts"), p.pI, p.pF, p.pO, hard ? 1 : 0, (int)s.B, (int)s.C,
+                                         (int)s.H, (int)s.W, (int)s.k, stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported shape (C % 16 == 0, odd k <= 7)");
+}
+// UT16: [C, k, k, 4C] (transpose_krsc of U16; the kernel flips the taps). dc is updated in place; dg16_out must not
+// alias dg16_next.
+void convlstm_bwd_step(const Tensor& UT16, const OptT& dg16_next, const OptT& dout, const OptT& dh_ext, const Tensor& acts,
+                       const Tensor& c_prev, const Tensor& c_t, const Tensor& dc, const Tensor& dg16_out, const OptT& pI,
+                       const OptT& pF, const OptT& pO, bool hard) {
+  const char* fn = "convlstm_bwd_step";
+  TORCH_CHECK(UT16.dim() == 4 && UT16.is_contiguous() && UT16.size(1) == UT16.size(2) && UT16.size(3) == 4 * UT16.size(0) &&
+                  (uintptr_t)UT16.data_ptr() % 16 == 0, fn, ": UT16 must be [C, k, k, 4C] contiguous");
+  TORCH_CHECK(c_t.dim() == 4, fn, ": c_t must be [B, H, W, C]");
+  const ConvLstmShape s{c_t.size(0), c_t.size(1), c_t.size(2), UT16.size(0), UT16.size(1)};
+  convlstm_opt(fn, dg16_next, s, 4 * s.C, "dg16_next"); convlstm_opt(fn, dout, s, s.C, "dout");
+  convlstm_opt(fn, dh_ext, s, s.C, "dh_ext"); convlstm_dense(fn, acts, s, 4 * s.C, "acts");
+  convlstm_dense(fn, c_prev, s, s.C, "c_prev"); convlstm_dense(fn, c_t, s, s.C, "c_t");
+  convlstm_dense(fn, dc, s, s.C, "dc"); convlstm_dense(fn, dg16_out, s, 4 * s.C, "dg16_out");
+  if (dg16_next && dg16_next->defined())
+    TORCH_CHECK(dg16_next->data_ptr() != dg16_out.data_ptr(), fn, ": dg16_out must not alias dg16_next");
+  const ConvLstmPeep p = convlstm_peep(fn, pI, pF, pO, s.C);
+  const int rc = bigdl_convlstm_bwd_step(cbf(UT16, "UT16"), ocbf(dg16_next, "dg16_next"), ocf(dout, "dout"),
+                                         ocf(dh_ext, "dh_ext"), cf(acts, "acts"), cf(c_prev, "c_prev"), cf(c_t, "c_t"),
+                                         mf(dc, "dc"), mbf(dg16_out, "dg16_out"), p.pI, p.pF, p.pO, hard ? 1 : 0,
+                                         (int)s.B, (int)s.C, (int)s.H, (int)s.W, (int)s.k, stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported shape (C % 16 == 0, odd k <= 7)");
+}
+// Peephole gradients out [3, C] = (dp_i, dp_f, dp_o) from dg16 [T, P, 4C] bf16, cs [T, P, C], c0 [P, C] (P = B H W
+// pixels); part = fp32 workspace of convlstm_peep_wgrad_slices(T * P) * 3 * C elements. Fixed order, no atomics.
+int64_t convlstm_peep_wgrad_slices(int64_t rows) { return bigdl_convlstm_peep_wgrad_slices(rows); }
+void convlstm_peep_wgrad(const Tensor& dg16, const Tensor& cs, const OptT& c0, const Tensor& part, const Tensor& out) {
+  const char* fn = "convlstm_peep_wgrad";
+  TORCH_CHECK(dg16.dim() == 3 && cs.dim() == 3 && dg16.is_contiguous() && cs.is_contiguous(), fn,
+              ": dg16 [T, P, 4C] and cs [T, P, C] must be contiguous");
+  const int64_t T = cs.size(0), P = cs.size(1), C = cs.size(2);
+  TORCH_CHECK(T >= 1 && P >= 1 && C > 0 && C % 16 == 0, fn, ": C must be a multiple of 16, T, P >= 1");
+  TORCH_CHECK(dg16.size(0) == T && dg16.size(1) == P && dg16.size(2) == 4 * C, fn, ": shapes");
+  if (c0 && c0->defined()) TORCH_CHECK(c0->numel() == P * C && c0->is_contiguous(), fn, ": c0 must be [P, C]");
+  TORCH_CHECK(part.is_contiguous() && part.numel() >= bigdl_convlstm_peep_wgrad_slices(T * P) * 3 * C, fn, ": part");
+  TORCH_CHECK(out.is_contiguous() && out.numel() == 3 * C, fn, ": out must be [3, C] contiguous");
+  const int rc = bigdl_convlstm_peep_wgrad(cbf(dg16, "dg16"), cf(cs, "cs"), ocf(c0, "c0"), mf(part, "part"),
+                                           mf(out, "out"), (long)T, (long)P, (int)C, stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported arguments");
+}
+
 // Whole-sequence persistent GRU (csrc/lstm_seq.hip): Wrz16 [2H, H], Wn16 [H, H] bf16; xg [B, T, 3H] f32 (r|z|n),
 // h16 [T + 1, B, H] bf16 (h16[0] = h0), rh16 [T, B, H] bf16, gates [3, T, B, H] f32, out [B, T, H] f32.
 bool gru_seq_supported(int64_t B, int64_t H) { return bigdl_gru_seq_supported((int)B, (int)H) != 0; }
@@ -2323,6 +2409,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pO") = py::none(), py::arg("mask") = py::none(), py::arg("order") = std::vector<int64_t>{0, 2, 1, 3});
   m.def("lstm_peep_wgrad_slices", &lstm_peep_wgrad_slices);
   m.def("lstm_peep_wgrad", &lstm_peep_wgrad);
+  m.def("convlstm_fwd_step", &convlstm_fwd_step, py::arg("U16"), py::arg("h16"), py::arg("xg"), py::arg("c_prev"),
+        py::arg("c_out"), py::arg("h_out"), py::arg("h16_out"), py::arg("acts") = py::none(),
+        py::arg("pI") = py::none(), py::arg("pF") = py::none(), py::arg("pO") = py::none(), py::arg("hard") = false);
+  m.def("convlstm_bwd_step", &convlstm_bwd_step, py::arg("UT16"), py::arg("dg16_next"), py::arg("dout"),
+        py::arg("dh_ext"), py::arg("acts"), py::arg("c_prev"), py::arg("c_t"), py::arg("dc"), py::arg("dg16_out"),
+        py::arg("pI") = py::none(), py::arg("pF") = py::none(), py::arg("pO") = py::none(), py::arg("hard") = false);
+  m.def("convlstm_peep_wgrad_slices", &convlstm_peep_wgrad_slices);
+  m.def("convlstm_peep_wgrad", &convlstm_peep_wgrad);
   m.def("lstm_seq_supported", &lstm_seq_supported);
   m.def("set_lstm_seq", &bigdl_set_lstm_seq);
   m.def("lstm_seq_sync_words", &lstm_seq_sync_words);

@@ -580,6 +580,26 @@ int bigdl_lstm_bwd_step(const uint16_t* WT16, const uint16_t* dg16_next, const f
 int bigdl_lstm_peep_wgrad_slices(long rows);
 int bigdl_lstm_peep_wgrad(const float* dg, long dg_sb, long dg_st, const float* cs, const float* c0, float* part,
                           float* out, int gi, int gf, int gg, int go, int T, int B, int H, hipStream_t st);
+// Fused ConvLSTMPeephole steps (csrc/convlstm.hip): one launch per time step. Activations are dense channels-last over
+// P = B * H * W pixels: [P][C] or [P][4C] with gate blocks (i, f, g, o); C % 16 == 0, odd kernel extent k <= 7, stride 1,
+// zero "same" padding. hard = 1: the inner activation is clamp(0.2 a + 0.5, 0, 1) instead of the sigmoid.
+// Forward: U bf16 [4C][k][k][C]; pre = conv(h16, U) + xg (fp32, bias included); peepholes pI, pF on c_prev and pO on
+// c_t (all three or null); writes c_out, h_out (fp32), h16_out (bf16) and, unless null, the four gates to acts.
+int bigdl_convlstm_fwd_step(const uint16_t* U, const uint16_t* h16, const float* xg, const float* c_prev,
+                            float* c_out, uint16_t* h16_out, float* h_out, float* acts, const float* pI,
+                            const float* pF, const float* pO, int hard, int B, int C, int H, int W, int k,
+                            hipStream_t st);
+// Backward: UT bf16 [C][k][k][4C] (taps flipped on read); dh = conv(dg_next, UT) + dout + dh_ext (each may be null),
+// then the cell backward: dg_out bf16 [P][4C], dc [P][C] updated in place (dc_t -> dc_{t-1}).
+int bigdl_convlstm_bwd_step(const uint16_t* UT, const uint16_t* dg_next, const float* dout, const float* dh_ext,
+                            const float* acts, const float* c_prev, const float* c_t, float* dc, uint16_t* dg_out,
+                            const float* pI, const float* pF, const float* pO, int hard, int B, int C, int H, int W,
+                            int k, hipStream_t st);
+// Peephole gradients out[3][C] = (dp_i, dp_f, dp_o) from dg bf16 [T][P][4C], cs [T][P][C] and c0 [P][C] (or null);
+// part is a [slices(T * P)][3][C] workspace. Fixed summation order, no atomics.
+int bigdl_convlstm_peep_wgrad_slices(long rows);
+int bigdl_convlstm_peep_wgrad(const uint16_t* dg, const float* cs, const float* c0, float* part, float* out, long T,
+                              long P, int C, hipStream_t st);
 // Whole-sequence persistent LSTM (csrc/lstm_seq.hip): one launch per direction, W resident in VGPRs.
 int bigdl_lstm_seq_supported(int B, int H);
 void bigdl_set_lstm_seq(int v);
