@@ -1294,39 +1294,10 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_g3_kernel(WgradArgs a) {
   }
 }
 
-// dw += sum over splits of the workspace partials. Split group g (blockIdx.y) sums splits g, g+G, ... with two
-// independent accumulators; with G > 1 the groups meet in dw through fp32 atomics (G-way contention at most), so
-// tiny weights (64x64 with ~1000 splits) still spread the reduction over the whole chip.
-template <bool ALIGNED>
-__global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                                           long n4, int splits) {
-  const int g = blockIdx.y, G = gridDim.y;
-  const v4f* w4 = reinterpret_cast<const v4f*>(ws);
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    v4f s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-    int sp = g;
-    for (; sp + G < splits; sp += 2 * G) {
-      s0 += w4[(long)sp * n4 + i];
-      s1 += w4[(long)(sp + G) * n4 + i];
-    }
-    if (sp < splits) s0 += w4[(long)sp * n4 + i];
-    s0 += s1;
-    if (G > 1) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) unsafeAtomicAdd(dw + 4 * i + e, s0[e]);
-    } else if (ALIGNED) {
-      reinterpret_cast<v4f*>(dw)[i] += s0;
-    } else {   // dw is a view into the flat gradient buffer at a 4-byte-aligned offset
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dw[4 * i + e] += s0[e];
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Weight gradient on the phase-interleaved 256 x 256 tile of conv_nt_p8_kernel: dW[n][kk] = sum_p dy[p][n] x[p][kk]
 // (kk = (r, s, c) of KRSC, x gathered im2col-style), reduction over output pixels p in K-steps of 64, split over
-// pixel ranges per blockIdx.y (fp32 partials [split][Ncol][Kdim] summed by wgrad_reduce_kernel; one split adds into
+// pixel ranges per blockIdx.y (fp32 partials [split][Ncol][Kdim] summed by bigdl_split_reduce_f32; one split adds into
 // dw directly; the bias gradient goes out as fp32 atomics, one per column and split). 8 waves = 2 kk-halves x 4
 // n-quarters, 128 kk x 64 n per wave, MFMA A = x fragment (rows kk), B = dy fragment (columns n), so a lane ends up
 // with 4 consecutive kk of one n: 16-byte stores along dw's rows.
@@ -3205,15 +3176,9 @@ WgradChoice conv_wgrad_ladder(const WgradArgs* a) {
   return c;
 }
 
-void launch_wgrad_reduce(const WgradArgs& a, int groups, hipStream_t st) {
-  const long n4 = (long)a.Ncol * a.Kdim / 4;
-  const int blocks = (int)std::min<long>((n4 + 255) / 256, 8192);
-  // groups < 0: ~2048 reduce workgroups in total, >= 4 splits per group, <= 64-way atomic contention
-  if (groups < 0)
-    groups = (blocks >= 256 || bigdl_deterministic()) ? 1 : std::max(1, std::min({2048 / blocks, a.splits / 4, 64}));
-  const dim3 grid(blocks, groups);
-  if ((reinterpret_cast<uintptr_t>(a.dw) & 15) == 0) wgrad_reduce_kernel<true><<<grid, 256, 0, st>>>(a.ws, a.dw, n4, a.splits);
-  else wgrad_reduce_kernel<false><<<grid, 256, 0, st>>>(a.ws, a.dw, n4, a.splits);
+// dw += the [splits][Ncol][Kdim] workspace partials, in a fixed order (split_reduce.hip)
+void launch_wgrad_reduce(const WgradArgs& a, hipStream_t st) {
+  bigdl_split_reduce_f32(a.ws, a.dw, (long)a.Ncol * a.Kdim, nullptr, 0, a.splits, st);
 }
 
 }  // namespace
@@ -3431,14 +3396,14 @@ int bigdl_conv_wgrad(const WgradArgs* a_in, const WgradChoice* c, hipStream_t st
         if (direct) conv_wgrad_p8_kernel<true, false><<<grid, dim3(512), 0, st>>>(a);
         else conv_wgrad_p8_kernel<false, false><<<grid, dim3(512), 0, st>>>(a);
       }
-      if (a.splits > 1) launch_wgrad_reduce(a, 1, st);
+      if (a.splits > 1) launch_wgrad_reduce(a, st);
       break;
     }
     case WGRAD_GLDS_WS:
     case WGRAD_G3_WS:
       if (c->kernel == WGRAD_G3_WS) launch_wgrad_g3(a, tiles * spad, st);
       else launch_wgrad_glds(a, tiles * spad, st);
-      launch_wgrad_reduce(a, -1, st);
+      launch_wgrad_reduce(a, st);
       break;
     case WGRAD_GLDS_ATOMIC: launch_wgrad_glds(a, tiles * spad, st); break;
     case WGRAD_G3_ATOMIC: launch_wgrad_g3(a, tiles * spad, st); break;

@@ -309,7 +309,7 @@ int bigdl_stem_i8_applies(const ConvArgs* a, const I8Epi* ep);
 void bigdl_set_stem_i8(int v);
 int bigdl_stem_i8_f32(const ConvArgs* a, const I8Epi* ep, const float* img, int C, int W, float inv, hipStream_t st);
 int bigdl_stem_i8(const ConvArgs* a, const I8Epi* ep, hipStream_t st);
-void bigdl_split_reduce_f32(const float* ws, float* dw, long n, int splits, hipStream_t st);
+void bigdl_split_reduce_f32(const float* ws, float* dw, long n, float* dbias, long nb, int splits, hipStream_t st);
 int bigdl_maxpool_bwd_bnred_applies(int N, int H, int W, int C, int OH, int OW, int kh, int kw, int sh, int sw, int ph,
                                     int pw);
 void bigdl_maxpool_bwd_bnred(const uint16_t* dy, const uint8_t* idx, uint16_t* dx, int N, int C, int OH, int OW,

@@ -396,8 +396,7 @@ int bigdl_stem_wgrad(const WgradArgs* a, hipStream_t st) {
   } else {
     stem_wgrad_kernel<115, false><<<dim3(grid), dim3(448), 0, st>>>(*a);
   }
-  bigdl_split_reduce_f32(a->ws, a->dw, 64 * 224, grid, st);
-  if (a->dbias) bigdl_split_reduce_f32(a->ws + (size_t)grid * 64 * 224, a->dbias, 64, grid, st);
+  bigdl_split_reduce_f32(a->ws, a->dw, 64 * 224, a->dbias, 64, grid, st);
   return 0;
 }
 

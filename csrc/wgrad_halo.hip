@@ -23,8 +23,8 @@
 // KB / 64 output-channel groups of 64; a wave holds 9 x 4 16x16 accumulators (144 registers) and per 32 virtual
 // pixels issues 36 MFMAs against 26 transposed LDS reads (8 dy + 18 x). NS LDS stages fill the LDS budget (80 KB by
 // default, BIGDL_WGRAD_HALO_LDS); the DMA runs NS - 2 stages ahead with counted vmcnt waits and one barrier per stage.
-// Splits over image-row stages give ~256 workgroups; partials go to the workspace and wgrad_reduce_kernel sums them
-// in a fixed order (deterministic), one split adds into dW directly.
+// Splits over image-row stages give ~256 workgroups; partials go to the workspace and bigdl_split_reduce_f32
+// (split_reduce.hip) sums them in a fixed order (deterministic), one split adds into dW directly.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -366,42 +366,6 @@ __global__ __launch_bounds__(KB * 4, 1) void conv_wgrad_halo_kernel(WgradArgs a)
     }
 }
 
-// dw[i] += sum over splits of ws[split][i], in a fixed order (deterministic): a workgroup owns 16 float4 columns and
-// its 16 thread rows stride the splits (coalesced 256-byte rows), then a fixed-order sum of the 16 row partials.
-// ~n4 / 16 workgroups keep the chip busy even for a 64 x 576 weight with 256 splits (the per-column loop of
-// wgrad_reduce_kernel ran 36 workgroups there: 38 us for 38 MB).
-__global__ __launch_bounds__(256) void halo_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, long n4,
-                                                         int splits, int aligned) {
-  __shared__ v4f red[16][17];
-  const int e = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const long i = (long)blockIdx.x * 16 + e;
-  v4f s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s0, s3 = s0;
-  if (i < n4) {
-    const v4f* w4 = reinterpret_cast<const v4f*>(ws);
-    int sp = g;
-    // four independent loads in flight per trip (the partial rows are read once: latency, not bandwidth, bound)
-    for (; sp + 48 < splits; sp += 64) {
-      const v4f a0 = w4[(long)sp * n4 + i], a1 = w4[(long)(sp + 16) * n4 + i];
-      const v4f a2 = w4[(long)(sp + 32) * n4 + i], a3 = w4[(long)(sp + 48) * n4 + i];
-      s0 += a0; s1 += a1; s2 += a2; s3 += a3;
-    }
-    for (; sp < splits; sp += 16) s0 += w4[(long)sp * n4 + i];
-  }
-  red[g][e] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (g == 0 && i < n4) {
-    v4f t = red[0][e];
-#pragma unroll
-    for (int r = 1; r < 16; ++r) t += red[r][e];
-    if (aligned) {
-      reinterpret_cast<v4f*>(dw)[i] += t;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dw[4 * i + k] += t[k];
-    }
-  }
-}
-
 template <int W, int RB, int LDSKB>
 void launch_halo(const WgradArgs& a, hipStream_t st) {
   const int ntile = (a.Cs / 64) * (a.Ncol / (a.Ncol % 128 == 0 ? 128 : 64));
@@ -435,7 +399,7 @@ int halo_lds() {
   return v;
 }
 // BIGDL_WGRAD_HALO_ATOMIC=1: with splits > 1 the splits add into dW / dbias with fp32 atomics instead of writing
-// workspace partials for halo_reduce_kernel (one fp32 copy of dW per split written and re-read); never in
+// workspace partials for the split reduce (one fp32 copy of dW per split written and re-read); never in
 // deterministic mode (atomic order)
 bool halo_atomic() {
   static const int v = [] { const char* e = getenv("BIGDL_WGRAD_HALO_ATOMIC"); return e ? atoi(e) : 0; }();
@@ -499,25 +463,9 @@ int bigdl_wgrad_halo(const WgradArgs* a_in, hipStream_t st) {
     case 7: launch_halo_lds<7, 7>(*a, lds, st); break;
     default: return -1;
   }
-  if (a->splits > 1 && a->ws != nullptr) {
-    const long n4 = (long)a->Ncol * a->Kdim / 4;
-    const int aligned = (reinterpret_cast<uintptr_t>(a->dw) & 15) == 0;
-    halo_reduce_kernel<<<dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st>>>(a->ws, a->dw, n4, a->splits, aligned);
-    if (a->dbias)      // [splits][Ncol] bias partials: the same split-parallel reduce (Ncol % 4 == 0)
-      halo_reduce_kernel<<<dim3((unsigned)((a->Ncol / 4 + 15) / 16)), dim3(256), 0, st>>>(
-          a->ws + (size_t)a->splits * a->Ncol * a->Kdim, a->dbias, a->Ncol / 4, a->splits,
-          (reinterpret_cast<uintptr_t>(a->dbias) & 15) == 0);
-  }
+  if (a->splits > 1 && a->ws != nullptr)     // the [splits][Ncol] bias partials in the same launch (Ncol % 64 == 0)
+    bigdl_split_reduce_f32(a->ws, a->dw, (long)a->Ncol * a->Kdim, a->dbias, a->Ncol, a->splits, st);
   return 0;
-}
-
-// dw[i] += sum over s of ws[s * n + i] (n % 4 == 0) in a fixed order, split-parallel: the stem weight gradient's
-// per-workgroup partials (csrc/stem_fwd.hip) use the same reduce as the halo weight gradient
-void bigdl_split_reduce_f32(const float* ws, float* dw, long n, int splits, hipStream_t st) {
-  const long n4 = n / 4;
-  halo_reduce_kernel<<<dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st>>>(
-      ws, dw, n4, splits, (reinterpret_cast<uintptr_t>(dw) & 15) == 0);
-  HIP_LAUNCH_CHECK();
 }
 
 }  // extern "C"

@@ -34,9 +34,11 @@ def timed(fn, iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--mib", type=int, nargs="+", default=[51, 205, 411],
+                    help="buffer sizes in MiB (32: the split partials of one weight-gradient layer)")
     a = ap.parse_args()
     C_ = native.get()
-    for mb in (51, 205, 411):
+    for mb in a.mib:
         n = mb * 2**20
         dst = torch.empty(n, dtype=torch.uint8, device="cuda")
         src = torch.randint(0, 255, (n,), dtype=torch.uint8, device="cuda")
