@@ -21,7 +21,9 @@ reverse sweep instead of T small ones. LSTMPeephole (p == 0) and the maskZero LS
 the GPU (``_LSTMPeepSeq``: csrc/lstm.hip, one fused launch per step with peephole terms and a row mask in
 the cell epilogue); every other masked cell runs the generic loop. The 2-D ConvLSTMPeephole (stride 1, "same"
 padding, outputSize % 16 == 0) runs ``_ConvLSTMSeq``: csrc/convlstm.hip, one fused halo-convolution + cell launch per
-step and direction, every other convolution once per sequence.
+step and direction, every other convolution once per sequence. ConvLSTMPeephole3D takes the same shape of path when
+asked to (``set_convlstm3d_fused`` / BIGDL_CONVLSTM3D_FUSED=1 / Engine property ``bigdl.convlstm3d.fused``):
+``_ConvLSTM3dSeq`` on csrc/convlstm3d.hip and the native volumetric convolution; by default it stays on the loop.
 """
 import os
 
@@ -1222,6 +1224,208 @@ class _ConvLSTMSeq(torch.autograd.Function):
         return (dx, dh_rec, dc, dWi, db, dU, *dps, None)
 
 
+# ConvLSTMPeephole3D on the fused step kernels is opt-in: BIGDL_CONVLSTM3D_FUSED=1, set_convlstm3d_fused, or the
+# Engine property bigdl.convlstm3d.fused. Unset means DEFAULT_CONVLSTM3D_FUSED (the Python time loop).
+DEFAULT_CONVLSTM3D_FUSED = False
+_CONVLSTM3D_FUSED = [None]
+
+
+def set_convlstm3d_fused(v):
+    """True / False, "1" / "0", or None for the default."""
+    _CONVLSTM3D_FUSED[0] = None if v is None or v == "" else str(v).lower() in ("1", "true", "yes")
+
+
+def convlstm3d_fused():
+    v = _CONVLSTM3D_FUSED[0]
+    if v is None:
+        env = os.environ.get("BIGDL_CONVLSTM3D_FUSED", "")
+        v = DEFAULT_CONVLSTM3D_FUSED if env == "" else env.lower() in ("1", "true", "yes")
+    return bool(v)
+
+
+class _ConvLSTM3dSeq(torch.autograd.Function):
+    """Whole-sequence ConvLSTMPeephole3D: x [B, T, Cin, D, H, W]; the semantics, arguments and results are those of
+    ``_ConvLSTMSeq`` with one more spatial dimension.
+
+    GPU (fp32 x, C % 16 == 0, a kernelC the step kernel serves): csrc/convlstm3d.hip, one fused launch per step and
+    direction on time-major channels-last [T, B, D, H, W, .] buffers. Once per sequence, with T * B folded into the
+    batch, on the native volumetric convolution (csrc/conv3d.hip): the input projection (fp32, bias included), dU over
+    the stacked (dg, h_{0..T-1}), dW / db over (dg, x), dx and dh_0; the peephole gradients by the 2-D reduction over
+    P = B D H W rows. The output is a channels-last-strided view of the time-major buffer.
+    Other tensors: the same forward and hand-derived backward in plain torch, in the tensors' own dtype."""
+
+    @staticmethod
+    def usable(x, cell, mask=None):
+        from types import SimpleNamespace as NS
+
+        from ..ops.conv_fn import _native3d
+
+        kI, kC, pad, C = cell.kernelI, cell.kernelC, cell.padding, cell.outputSize
+        if not (convlstm3d_fused() and cell._nd == 3 and mask is None and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 6 and x.shape[1] > 0 and C % 16 == 0 and cell.stride == 1
+                and kC % 2 == 1 and kI % 2 == 1 and (pad == -1 or 2 * pad == kI - 1 == kC - 1)
+                and _is(cell.activation, Tanh) and (_is(cell.innerActivation, Sigmoid)
+                                                    or _is(cell.innerActivation, HardSigmoid))):
+            return False
+        B, T, Cin, D, H, W = x.shape
+        # the once-per-sequence convolutions see T * B volumes: both must be inside the native kernels' index range
+        return (ops.native.get().convlstm3d_supported(B, C, D, H, W, kC)
+                and _native3d(NS(shape=(T * B, Cin, D, H, W)), cell.i2g.weight, (1, 1, 1), ((kI - 1) // 2,) * 3)
+                and _native3d(NS(shape=(T * B, C, D, H, W)), cell.h2g.weight, (1, 1, 1), ((kC - 1) // 2,) * 3))
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, Wi, bi, U, pI, pF, pO, hard):
+        ctx.set_materialize_grads(False)
+        B, T, Cin, D, H, W = x.shape
+        C = U.shape[0] // 4
+        kI, kC = Wi.shape[2], U.shape[2]
+        peep = pI is not None
+        assert (pF is not None) == peep and (pO is not None) == peep, "peepholes: all three or none"
+        ctx.peep, ctx.hard, ctx.has_bias = peep, bool(hard), bi is not None
+        ctx.pshapes = [p.shape for p in (pI, pF, pO)] if peep else None
+        ctx.fused = (x.is_cuda and x.dtype == torch.float32 and C % 16 == 0
+                     and ops.native.get().convlstm3d_supported(B, C, D, H, W, kC))
+        if ctx.fused:
+            from ..ops import conv_fn as cf
+
+            N = ops.native.get()
+            train = any(ctx.needs_input_grad)
+            # time-major from here on: step t is one dense [B, D, H, W, .] slab of every buffer
+            x16 = cf._ndhwc16(x.detach().transpose(0, 1).reshape(T * B, Cin, D, H, W), cf._p8(Cin))
+            Wi16 = cf._w3d16(Wi.detach(), 4 * C, x16.shape[-1])        # [4C, k, k, k, Cin8]
+            U16 = cf._w3d16(U.detach(), 4 * C, C)                       # [4C, k, k, k, C]
+            # fp32 projection (a bf16-rounded pre-activation would move elements across the hard-sigmoid's kinks);
+            # 4C is a multiple of 8, so the convolution's output is xg as it lies
+            xg = x.new_empty(T * B, D, H, W, 4 * C)
+            N.conv3d_fwd(x16, Wi16, bi.detach().float().contiguous() if bi is not None else None, xg,
+                         [1, 1, 1] + [(kI - 1) // 2] * 3)
+            xg = xg.view(T, B, D, H, W, 4 * C)
+            ps = [p.detach().reshape(C).contiguous() for p in (pI, pF, pO)] if peep else [None, None, None]
+            out = x.new_empty(T, B, D, H, W, C)
+            cs = x.new_empty(T, B, D, H, W, C)
+            acts = x.new_empty(T, B, D, H, W, 4 * C) if train else None
+            h16 = x.new_empty(T + 1, B, D, H, W, C, dtype=torch.bfloat16)
+            h16[0].copy_(h0.detach().permute(0, 2, 3, 4, 1))
+            c0n = c0.detach().permute(0, 2, 3, 4, 1).contiguous()
+            for t in range(T):
+                N.convlstm3d_fwd_step(U16, h16[t], xg[t], cs[t - 1] if t > 0 else c0n, cs[t], out[t], h16[t + 1],
+                                      acts[t] if train else None, pI=ps[0], pF=ps[1], pO=ps[2], hard=ctx.hard)
+            if train:
+                ctx.save_for_backward(x16, Wi16, U16, c0n, cs, acts, h16, *ps)
+                ctx.cin = Cin
+            return (out.permute(1, 0, 5, 2, 3, 4), out[-1].permute(0, 4, 1, 2, 3).contiguous(),
+                    cs[-1].permute(0, 4, 1, 2, 3).contiguous())
+        inner = _ConvLSTMSeq._inner
+        xg = F.conv3d(x.reshape(B * T, Cin, D, H, W), Wi, bi, padding=(kI - 1) // 2).view(B, T, 4 * C, D, H, W)
+        h, c = h0, c0
+        hs, cs, gi, gf, gg, go = ([] for _ in range(6))
+        for t in range(T):
+            g = xg[:, t] + F.conv3d(h, U, None, padding=(kC - 1) // 2)
+            ai, af = g[:, :C], g[:, C:2 * C]
+            if peep:
+                ai, af = ai + pI * c, af + pF * c
+            i, f, gc = inner(ai, hard), inner(af, hard), torch.tanh(g[:, 2 * C:3 * C])
+            c = f * c + i * gc
+            ao = g[:, 3 * C:]
+            if peep:
+                ao = ao + pO * c
+            o = inner(ao, hard)
+            h = o * torch.tanh(c)
+            hs.append(h); cs.append(c); gi.append(i); gf.append(f); gg.append(gc); go.append(o)
+        hs, cs = torch.stack(hs), torch.stack(cs)
+        ctx.save_for_backward(x, h0, c0, Wi, U, hs, cs, torch.stack(gi), torch.stack(gf), torch.stack(gg),
+                              torch.stack(go), pI, pF, pO)
+        return hs.transpose(0, 1).contiguous(), hs[-1].clone(), cs[-1].clone()
+
+    @staticmethod
+    def _backward_fused(ctx, dout, dhT, dcT):
+        from ..ops import conv_fn as cf
+
+        x16, Wi16, U16, c0n, cs, acts, h16, pI, pF, pO = ctx.saved_tensors
+        T, B, D, H, W, C = cs.shape
+        N = ops.native.get()
+        geoI, geoC = [1, 1, 1] + [(Wi16.shape[1] - 1) // 2] * 3, [1, 1, 1] + [(U16.shape[1] - 1) // 2] * 3
+        if dout is not None:
+            dout = dout.permute(1, 0, 3, 4, 5, 2).contiguous()     # no copy for a gradient laid out like the output
+        dhT = dhT.permute(0, 2, 3, 4, 1).contiguous() if dhT is not None else None
+        # dc is updated in place by every step: always a private channels-last copy of the incoming gradient
+        dc = dcT.permute(0, 2, 3, 4, 1).clone(memory_format=torch.contiguous_format) if dcT is not None \
+            else ops.zeros(B, D, H, W, C, device=cs.device)
+        UT16 = U16.permute(4, 1, 2, 3, 0).contiguous()             # [C, k, k, k, 4C]
+        dg16 = cs.new_empty(T, B, D, H, W, 4 * C, dtype=torch.bfloat16)
+        for t in range(T - 1, -1, -1):
+            N.convlstm3d_bwd_step(UT16, dg16[t + 1] if t < T - 1 else None, dout[t] if dout is not None else None,
+                                  dhT if t == T - 1 else None, acts[t], cs[t - 1] if t > 0 else c0n, cs[t], dc,
+                                  dg16[t], pI=pI, pF=pF, pO=pO, hard=ctx.hard)
+        dg = dg16.view(T * B, D, H, W, 4 * C)                      # gate gradients of all steps
+        need = ctx.needs_input_grad                                 # x, h0, c0, Wi, bi, U, pI, pF, pO
+        dx = dh0 = dU = dWi = db = None
+        if need[1]:
+            dh0 = cs.new_empty(B, D, H, W, C)
+            N.conv3d_dgrad(dg16[0], UT16, None, dh0, geoC)
+            dh0 = dh0.permute(0, 4, 1, 2, 3)
+        if need[5]:
+            dU = cf._wgrad3d(dg, h16[:T].view(T * B, D, H, W, C), U16.shape, geoC, False)[0].permute(0, 4, 1, 2, 3)
+        if need[3] or (ctx.has_bias and need[4]):
+            dWi, db = cf._wgrad3d(dg, x16, Wi16.shape, geoI, ctx.has_bias)
+            dWi = dWi[..., :ctx.cin].permute(0, 4, 1, 2, 3)
+        if need[0]:
+            dx = cs.new_empty(x16.shape)
+            N.conv3d_dgrad(dg, Wi16.permute(4, 1, 2, 3, 0).contiguous(), None, dx, geoI)
+            dx = dx.view(T, B, D, H, W, -1).permute(1, 0, 5, 2, 3, 4)[:, :, :ctx.cin]
+        dps = [None, None, None]
+        if ctx.peep and any(need[6:9]):
+            P = B * D * H * W
+            part = cs.new_empty(N.convlstm_peep_wgrad_slices(T * P), 3, C)
+            dp = cs.new_empty(3, C)
+            N.convlstm_peep_wgrad(dg16.view(T, P, 4 * C), cs.view(T, P, C), c0n.view(P, C), part, dp)
+            dps = [dp[k].reshape(s) for k, s in enumerate(ctx.pshapes)]
+        return (dx, dh0, dc.permute(0, 4, 1, 2, 3), dWi, db, dU, *dps, None)
+
+    @staticmethod
+    def backward(ctx, dout, dhT, dcT):
+        if ctx.fused:
+            return _ConvLSTM3dSeq._backward_fused(ctx, dout, dhT, dcT)
+        x, h0, c0, Wi, U, hs, cs, gi, gf, gg, go, pI, pF, pO = ctx.saved_tensors
+        T, B, C = hs.shape[:3]
+        vol = hs.shape[3:]
+        peep, hard = ctx.peep, ctx.hard
+        igrad = _ConvLSTMSeq._inner_grad
+        padI, padC = (Wi.shape[2] - 1) // 2, (U.shape[2] - 1) // 2
+        dh_rec = dhT if dhT is not None else torch.zeros_like(h0)
+        dc = dcT if dcT is not None else torch.zeros_like(c0)
+        dgs = hs.new_zeros(T, B, 4 * C, *vol)
+        dps = [torch.zeros_like(pI), torch.zeros_like(pF), torch.zeros_like(pO)] if peep else [None, None, None]
+        for t in range(T - 1, -1, -1):
+            c_prev = cs[t - 1] if t > 0 else c0
+            i, f, gc, o, c = gi[t], gf[t], gg[t], go[t], cs[t]
+            dh = dh_rec + dout[:, t] if dout is not None else dh_rec
+            tc = torch.tanh(c)
+            do_ = dh * tc * igrad(o, hard)
+            dcv = dh * o * (1 - tc * tc) + dc
+            if peep:
+                dcv = dcv + do_ * pO
+            di_ = dcv * gc * igrad(i, hard)
+            df_ = dcv * c_prev * igrad(f, hard)
+            dg_ = dcv * i * (1 - gc * gc)
+            dc = dcv * f
+            if peep:
+                dc = dc + di_ * pI + df_ * pF
+                dps[0] = dps[0] + (di_ * c_prev).sum((0, 2, 3, 4)).reshape(pI.shape)
+                dps[1] = dps[1] + (df_ * c_prev).sum((0, 2, 3, 4)).reshape(pF.shape)
+                dps[2] = dps[2] + (do_ * c).sum((0, 2, 3, 4)).reshape(pO.shape)
+            dgs[t] = torch.cat([di_, df_, dg_, do_], 1)
+            dh_rec = torch.nn.grad.conv3d_input(h0.shape, U, dgs[t], padding=padC)
+        hprev = torch.cat([h0.unsqueeze(0), hs[:-1]], 0).reshape(T * B, C, *vol)
+        dU = torch.nn.grad.conv3d_weight(hprev, U.shape, dgs.reshape(T * B, 4 * C, *vol), padding=padC)
+        dgb = dgs.transpose(0, 1).reshape(B * T, 4 * C, *vol)                   # batch-major like x
+        xf = x.reshape(B * T, x.shape[2], *vol)
+        dWi = torch.nn.grad.conv3d_weight(xf, Wi.shape, dgb, padding=padI)
+        db = dgb.sum((0, 2, 3, 4)) if ctx.has_bias else None
+        dx = torch.nn.grad.conv3d_input(xf.shape, Wi, dgb, padding=padI).view(x.shape)
+        return (dx, dh_rec, dc, dWi, db, dU, *dps, None)
+
+
 class _ConvLSTMBase(Cell):
     _nd = 2
 
@@ -1296,11 +1500,13 @@ class _ConvLSTMBase(Cell):
         return h2, [h2, c2]
 
     def sequence(self, x2, hid, mask=None):
-        if _ConvLSTMSeq.usable(x2, self, mask):
-            # GPU, 2-D: one fused step kernel per time step and direction (csrc/convlstm.hip)
+        # GPU: one fused step kernel per time step and direction (2-D: csrc/convlstm.hip; 3-D, opt-in:
+        # csrc/convlstm3d.hip)
+        seq = next((s for s in (_ConvLSTMSeq, _ConvLSTM3dSeq) if s.usable(x2, self, mask)), None)
+        if seq is not None:
             peep = [self.peepI.weight, self.peepF.weight, self.peepO.weight] if self.withPeephole else [None] * 3
-            out, h, c = _ConvLSTMSeq.apply(x2, hid[0], hid[1], self.i2g.weight, self.i2g.bias, self.h2g.weight, *peep,
-                                           _is(self.innerActivation, HardSigmoid))
+            out, h, c = seq.apply(x2, hid[0], hid[1], self.i2g.weight, self.i2g.bias, self.h2g.weight, *peep,
+                                  _is(self.innerActivation, HardSigmoid))
             return out, [h, c]
         return super().sequence(x2, hid, mask)
 

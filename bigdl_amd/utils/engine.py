@@ -183,6 +183,10 @@ class _Engine:
             from ..ops import sparse
 
             sparse.set_native(v)
+        elif k == "bigdl.convlstm3d.fused":         # ConvLSTMPeephole3D sequences on the fused step kernels
+            from ..nn import recurrent
+
+            recurrent.set_convlstm3d_fused(v)
         elif k == "bigdl.module.deviceTiming":      # getTimes in device time (HIP events) for GPU modules
             from ..nn import abstractnn
 

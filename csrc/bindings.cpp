@@ -1855,6 +1855,66 @@ void convlstm_bwd_step(const Tensor& UT16, const OptT& dg16_next, const OptT& do
                                          (int)s.B, (int)s.C, (int)s.H, (int)s.W, (int)s.k, stream());
   TORCH_CHECK(rc == 0, fn, ": unsupported shape (C % 16 == 0, odd k <= 7)");
 }
+// Fused ConvLSTMPeephole3D steps (csrc/convlstm3d.hip): the 2-D steps over dense [B, D, H, W, C] / [B, D, H, W, 4C]
+// activations; U16 [4C, k, k, k, C], UT16 [C, k, k, k, 4C]. The peephole checks are the 2-D ones.
+struct ConvLstm3dShape { int64_t B, D, H, W, C, k; };
+void convlstm3d_dense(const char* fn, const Tensor& t, const ConvLstm3dShape& s, int64_t ch, const char* name) {
+  TORCH_CHECK(t.dim() == 5 && t.size(0) == s.B && t.size(1) == s.D && t.size(2) == s.H && t.size(3) == s.W &&
+                  t.size(4) == ch && t.is_contiguous() && (uintptr_t)t.data_ptr() % 16 == 0,
+              fn, ": ", name, " must be a dense 16-byte aligned [B, D, H, W, ", ch, "] tensor");
+}
+void convlstm3d_opt(const char* fn, const OptT& t, const ConvLstm3dShape& s, int64_t ch, const char* name) {
+  if (t && t->defined()) convlstm3d_dense(fn, *t, s, ch, name);
+}
+ConvLstm3dShape convlstm3d_shape(const char* fn, const Tensor& w, bool transposed, const Tensor& act) {
+  const int64_t C = w.dim() == 5 ? w.size(transposed ? 0 : 4) : 0;
+  TORCH_CHECK(w.dim() == 5 && w.is_contiguous() && w.size(1) == w.size(2) && w.size(1) == w.size(3) &&
+                  w.size(transposed ? 4 : 0) == 4 * C && (uintptr_t)w.data_ptr() % 16 == 0,
+              fn, transposed ? ": UT16 must be [C, k, k, k, 4C] contiguous" : ": U16 must be [4C, k, k, k, C] contiguous");
+  TORCH_CHECK(act.dim() == 5, fn, ": activations must be [B, D, H, W, C]");
+  for (int i = 0; i < 4; ++i) TORCH_CHECK(act.size(i) < (1ll << 31), fn, ": extent out of range");
+  return ConvLstm3dShape{act.size(0), act.size(1), act.size(2), act.size(3), C, w.size(1)};
+}
+bool convlstm3d_supported(int64_t B, int64_t C, int64_t D, int64_t H, int64_t W, int64_t k) {
+  for (int64_t v : {B, C, D, H, W, k})
+    if (v < 0 || v >= (1ll << 31)) return false;
+  return bigdl_convlstm3d_supported((int)B, (int)C, (int)D, (int)H, (int)W, (int)k) != 0;
+}
+void convlstm3d_fwd_step(const Tensor& U16, const Tensor& h16, const Tensor& xg, const Tensor& c_prev, const Tensor& c_out,
+                         const Tensor& h_out, const Tensor& h16_out, const OptT& acts, const OptT& pI, const OptT& pF,
+                         const OptT& pO, bool hard) {
+  const char* fn = "convlstm3d_fwd_step";
+  const ConvLstm3dShape s = convlstm3d_shape(fn, U16, false, h16);
+  convlstm3d_dense(fn, h16, s, s.C, "h16"); convlstm3d_dense(fn, xg, s, 4 * s.C, "xg");
+  convlstm3d_dense(fn, c_prev, s, s.C, "c_prev"); convlstm3d_dense(fn, c_out, s, s.C, "c_out");
+  convlstm3d_dense(fn, h_out, s, s.C, "h_out"); convlstm3d_dense(fn, h16_out, s, s.C, "h16_out");
+  convlstm3d_opt(fn, acts, s, 4 * s.C, "acts");
+  TORCH_CHECK(h16_out.data_ptr() != h16.data_ptr(), fn, ": h16_out must not alias h16 (neighbouring tiles read it)");
+  const ConvLstmPeep p = convlstm_peep(fn, pI, pF, pO, s.C);
+  const int rc = bigdl_convlstm3d_fwd_step(cbf(U16, "U16"), cbf(h16, "h16"), cf(xg, "xg"), cf(c_prev, "c_prev"),
+                                           mf(c_out, "c_out"), mbf(h16_out, "h16_out"), mf(h_out, "h_out"),
+                                           omf(acts, "acts"), p.pI, p.pF, p.pO, hard ? 1 : 0, (int)s.B, (int)s.C,
+                                           (int)s.D, (int)s.H, (int)s.W, (int)s.k, stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported shape (C % 16 == 0, odd k <= 7 whose staged tile fits the LDS)");
+}
+void convlstm3d_bwd_step(const Tensor& UT16, const OptT& dg16_next, const OptT& dout, const OptT& dh_ext, const Tensor& acts,
+                         const Tensor& c_prev, const Tensor& c_t, const Tensor& dc, const Tensor& dg16_out, const OptT& pI,
+                         const OptT& pF, const OptT& pO, bool hard) {
+  const char* fn = "convlstm3d_bwd_step";
+  const ConvLstm3dShape s = convlstm3d_shape(fn, UT16, true, c_t);
+  convlstm3d_opt(fn, dg16_next, s, 4 * s.C, "dg16_next"); convlstm3d_opt(fn, dout, s, s.C, "dout");
+  convlstm3d_opt(fn, dh_ext, s, s.C, "dh_ext"); convlstm3d_dense(fn, acts, s, 4 * s.C, "acts");
+  convlstm3d_dense(fn, c_prev, s, s.C, "c_prev"); convlstm3d_dense(fn, c_t, s, s.C, "c_t");
+  convlstm3d_dense(fn, dc, s, s.C, "dc"); convlstm3d_dense(fn, dg16_out, s, 4 * s.C, "dg16_out");
+  if (dg16_next && dg16_next->defined())
+    TORCH_CHECK(dg16_next->data_ptr() != dg16_out.data_ptr(), fn, ": dg16_out must not alias dg16_next");
+  const ConvLstmPeep p = convlstm_peep(fn, pI, pF, pO, s.C);
+  const int rc = bigdl_convlstm3d_bwd_step(cbf(UT16, "UT16"), ocbf(dg16_next, "dg16_next"), ocf(dout, "dout"),
+                                           ocf(dh_ext, "dh_ext"), cf(acts, "acts"), cf(c_prev, "c_prev"), cf(c_t, "c_t"),
+                                           mf(dc, "dc"), mbf(dg16_out, "dg16_out"), p.pI, p.pF, p.pO, hard ? 1 : 0,
+                                           (int)s.B, (int)s.C, (int)s.D, (int)s.H, (int)s.W, (int)s.k, stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported shape (C % 16 == 0, odd k <= 7 whose staged tile fits the LDS)");
+}
 // Peephole gradients out [3, C] = (dp_i, dp_f, dp_o) from dg16 [T, P, 4C] bf16, cs [T, P, C], c0 [P, C] (P = B H W
 // pixels); part = fp32 workspace of convlstm_peep_wgrad_slices(T * P) * 3 * C elements. Fixed order, no atomics.
 int64_t convlstm_peep_wgrad_slices(int64_t rows) { return bigdl_convlstm_peep_wgrad_slices(rows); }
@@ -2413,6 +2473,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("c_out"), py::arg("h_out"), py::arg("h16_out"), py::arg("acts") = py::none(),
         py::arg("pI") = py::none(), py::arg("pF") = py::none(), py::arg("pO") = py::none(), py::arg("hard") = false);
   m.def("convlstm_bwd_step", &convlstm_bwd_step, py::arg("UT16"), py::arg("dg16_next"), py::arg("dout"),
+        py::arg("dh_ext"), py::arg("acts"), py::arg("c_prev"), py::arg("c_t"), py::arg("dc"), py::arg("dg16_out"),
+        py::arg("pI") = py::none(), py::arg("pF") = py::none(), py::arg("pO") = py::none(), py::arg("hard") = false);
+  m.def("convlstm3d_supported", &convlstm3d_supported, py::arg("B"), py::arg("C"), py::arg("D"), py::arg("H"),
+        py::arg("W"), py::arg("k"));
+  m.def("convlstm3d_fwd_step", &convlstm3d_fwd_step, py::arg("U16"), py::arg("h16"), py::arg("xg"), py::arg("c_prev"),
+        py::arg("c_out"), py::arg("h_out"), py::arg("h16_out"), py::arg("acts") = py::none(),
+        py::arg("pI") = py::none(), py::arg("pF") = py::none(), py::arg("pO") = py::none(), py::arg("hard") = false);
+  m.def("convlstm3d_bwd_step", &convlstm3d_bwd_step, py::arg("UT16"), py::arg("dg16_next"), py::arg("dout"),
         py::arg("dh_ext"), py::arg("acts"), py::arg("c_prev"), py::arg("c_t"), py::arg("dc"), py::arg("dg16_out"),
         py::arg("pI") = py::none(), py::arg("pF") = py::none(), py::arg("pO") = py::none(), py::arg("hard") = false);
   m.def("convlstm_peep_wgrad_slices", &convlstm_peep_wgrad_slices);

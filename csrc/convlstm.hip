@@ -39,21 +39,14 @@
 #endif
 #include "common.h"
 #include "kernels.h"
-#include "rnn_step.h"
+#include "convlstm_cell.h"
 
 namespace {
 
+using namespace convlstm_cell;
+
 constexpr int TM = 128;        // virtual pixels per workgroup
 constexpr int FM = TM / 16;    // pixel fragments per wave
-
-__device__ __forceinline__ void wg_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// granule slot swizzle of a 64-byte LDS row (conv_halo.hip): conflict-free 16-row fragment reads at any row offset
-__device__ __forceinline__ int hswz(int r) { return ((r >> 2) & 1) << 1; }
 
 struct Geo {
   int B, H, W, k;    // images, image extent, kernel extent (odd)
@@ -140,26 +133,6 @@ __device__ __forceinline__ void halo_gemm(const Geo& g, const bf16_t* __restrict
   }
 }
 
-template <bool HARD>
-__device__ __forceinline__ float inner_act(float x) {
-  if constexpr (HARD) return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f);
-  else return sigm(x);
-}
-// derivative of the inner activation from its saved value
-template <bool HARD>
-__device__ __forceinline__ float inner_grad(float s) {
-  if constexpr (HARD) return (s > 0.f && s < 1.f) ? 0.2f : 0.f;
-  else return s * (1.f - s);
-}
-
-// bf16 bits -> fp32 by bit cast (the runtime header's __uint_as_float does not carry this file's target attribute
-// and would stay a call)
-__device__ __forceinline__ float bits_f(unsigned u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ v4f ld4f(const float* p) { return *(const v4f*)p; }
-__device__ __forceinline__ void st4bf(bf16_t* p, const v4f& v) {
-  *(v2u*)p = v2u{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-}
-
 struct FwdArgs {
   const bf16_t* U;       // [4C][k][k][C]
   const bf16_t* h16;     // [P][C]     h_{t-1}
@@ -206,30 +179,7 @@ __global__ __launch_bounds__(256) void convlstm_fwd_step_kernel(FwdArgs a) {
   for (int i = 0; i < FM; ++i) {
     const int P = pix[rc + 16 * i];
     if (P < 0) continue;
-    const long pc = (long)P * C + c4, pg = (long)P * 4 * C + c4;
-    const v4f xi = ld4f(a.xg + pg), xf = ld4f(a.xg + pg + C), xc = ld4f(a.xg + pg + 2 * C), xo = ld4f(a.xg + pg + 3 * C);
-    const v4f cp = ld4f(a.c_prev + pc);
-    v4f gi, gf, gg, go, c, h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float ai = acc[0][i][e] + xi[e], af = acc[1][i][e] + xf[e];
-      if (peep) { ai += wi[e] * cp[e]; af += wf[e] * cp[e]; }
-      gi[e] = inner_act<HARD>(ai);
-      gf[e] = inner_act<HARD>(af);
-      gg[e] = tanh_f(acc[2][i][e] + xc[e]);
-      c[e] = gf[e] * cp[e] + gi[e] * gg[e];
-      float ao = acc[3][i][e] + xo[e];
-      if (peep) ao += wo[e] * c[e];
-      go[e] = inner_act<HARD>(ao);
-      h[e] = go[e] * tanh_f(c[e]);
-    }
-    *(v4f*)(a.c_out + pc) = c;
-    *(v4f*)(a.h_out + pc) = h;
-    st4bf(a.h16_out + pc, h);
-    if (a.acts != nullptr) {
-      *(v4f*)(a.acts + pg) = gi; *(v4f*)(a.acts + pg + C) = gf;
-      *(v4f*)(a.acts + pg + 2 * C) = gg; *(v4f*)(a.acts + pg + 3 * C) = go;
-    }
+    cell_fwd<HARD>(a, P, c4, peep, wi, wf, wo, acc[0][i], acc[1][i], acc[2][i], acc[3][i]);
   }
 }
 
@@ -278,28 +228,7 @@ __global__ __launch_bounds__(256) void convlstm_bwd_step_kernel(BwdArgs a) {
   for (int i = 0; i < FM; ++i) {
     const int P = pix[rc + 16 * i];
     if (P < 0) continue;
-    const long pc = (long)P * C + c4, pg = (long)P * 4 * C + c4;
-    const v4f ig = ld4f(a.acts + pg), fg = ld4f(a.acts + pg + C), gg = ld4f(a.acts + pg + 2 * C), og = ld4f(a.acts + pg + 3 * C);
-    const v4f ct = ld4f(a.c_t + pc), cp = ld4f(a.c_prev + pc), dcn = ld4f(a.dc + pc);
-    v4f dh = acc[0][i];
-    if (a.dout != nullptr) { const v4f d = ld4f(a.dout + pc); dh += d; }
-    if (a.dh_ext != nullptr) { const v4f d = ld4f(a.dh_ext + pc); dh += d; }
-    v4f di, df, dgg, dog, dcp;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float tc = tanh_f(ct[e]);
-      dog[e] = dh[e] * tc * inner_grad<HARD>(og[e]);
-      float dcv = dh[e] * og[e] * (1.f - tc * tc) + dcn[e];
-      if (peep) dcv += dog[e] * wo[e];
-      di[e] = dcv * gg[e] * inner_grad<HARD>(ig[e]);
-      df[e] = dcv * cp[e] * inner_grad<HARD>(fg[e]);
-      dgg[e] = dcv * ig[e] * (1.f - gg[e] * gg[e]);
-      dcp[e] = dcv * fg[e];
-      if (peep) dcp[e] += di[e] * wi[e] + df[e] * wf[e];
-    }
-    *(v4f*)(a.dc + pc) = dcp;
-    st4bf(a.dg_out + pg, di); st4bf(a.dg_out + pg + C, df);
-    st4bf(a.dg_out + pg + 2 * C, dgg); st4bf(a.dg_out + pg + 3 * C, dog);
+    cell_bwd<HARD>(a, P, c4, peep, wi, wf, wo, acc[0][i]);
   }
 }
 

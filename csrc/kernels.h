@@ -600,6 +600,20 @@ int bigdl_convlstm_bwd_step(const uint16_t* UT, const uint16_t* dg_next, const f
 int bigdl_convlstm_peep_wgrad_slices(long rows);
 int bigdl_convlstm_peep_wgrad(const uint16_t* dg, const float* cs, const float* c0, float* part, float* out, long T,
                               long P, int C, hipStream_t st);
+// Fused ConvLSTMPeephole3D steps (csrc/convlstm3d.hip): the same steps over P = B * D * H * W voxels of dense
+// channels-last [B][D][H][W][.] activations, odd cubic kernel k; U bf16 [4C][k][k][k][C], UT bf16 [C][k][k][k][4C] (taps
+// flipped on read). k = 1 and 3 are served for any extent, k = 5 and 7 where the staged tile fits the LDS the device
+// grants a workgroup (160 KiB: k = 5 always): bigdl_convlstm3d_supported tells (1 / 0), and the steps return -1
+// without a launch otherwise. The peephole gradients are bigdl_convlstm_peep_wgrad's.
+int bigdl_convlstm3d_supported(int B, int C, int D, int H, int W, int k);
+int bigdl_convlstm3d_fwd_step(const uint16_t* U, const uint16_t* h16, const float* xg, const float* c_prev,
+                              float* c_out, uint16_t* h16_out, float* h_out, float* acts, const float* pI,
+                              const float* pF, const float* pO, int hard, int B, int C, int D, int H, int W, int k,
+                              hipStream_t st);
+int bigdl_convlstm3d_bwd_step(const uint16_t* UT, const uint16_t* dg_next, const float* dout, const float* dh_ext,
+                              const float* acts, const float* c_prev, const float* c_t, float* dc, uint16_t* dg_out,
+                              const float* pI, const float* pF, const float* pO, int hard, int B, int C, int D, int H,
+                              int W, int k, hipStream_t st);
 // Whole-sequence persistent LSTM (csrc/lstm_seq.hip): one launch per direction, W resident in VGPRs.
 int bigdl_lstm_seq_supported(int B, int H);
 void bigdl_set_lstm_seq(int v);
