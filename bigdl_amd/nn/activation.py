@@ -106,7 +106,8 @@ class Threshold(_NativeActivation):
         self.threshold, self.value, self.inplace = th, v, ip
 
     def fn(self, x):
-        return torch.where(x > self.threshold, x, torch.full_like(x, self.value))
+        # x <= th ? v : x (S/nn/Threshold.scala:83): a NaN input passes, as in the native kernel
+        return torch.where(x <= self.threshold, torch.full_like(x, self.value), x)
 
 
 class BinaryThreshold(AutogradModule):

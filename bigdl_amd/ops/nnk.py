@@ -81,7 +81,7 @@ def dropout_gpu(x, p, scale, seed, out=None):
     """y = x * keep(seed) [/ (1-p)]; call again with the same seed on dy for the backward."""
     x = x.contiguous()
     out = torch.empty_like(x) if out is None else out
-    mul = 1.0 / (1.0 - p) if scale else 1.0
+    mul = 1.0 / (1.0 - p) if scale and p < 1.0 else 1.0      # p == 1 keeps nothing: the factor is never used
     native.get().dropout(x, out, float(p), float(mul), int(seed) & 0x7FFFFFFFFFFFFFFF)
     return out
 

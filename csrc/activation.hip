@@ -20,22 +20,24 @@ enum Act {
   A_TANHSHRINK, A_SOFTSHRINK, A_HARDSHRINK, A_THRESHOLD, A_EXP, A_LOG, A_SQRT, A_SQUARE, A_ABS
 };
 
+// The clamp-style kinds compare instead of fminf / fmaxf, so a NaN input stays a NaN (HardTanh.scala:93-97, the
+// in-place form; Threshold.scala:83 x <= th ? v : x) and -0 inside the window keeps its sign.
 __device__ __forceinline__ float act_f(int k, float x, float a, float b) {
   switch (k) {
     case A_TANH: return tanhf(x);
     case A_SIGMOID: return 1.f / (1.f + __expf(-x));
     case A_ELU: return x > 0.f ? x : a * (__expf(x) - 1.f);
     case A_LEAKY: return x > 0.f ? x : a * x;
-    case A_RELU6: return fminf(fmaxf(x, 0.f), 6.f);
+    case A_RELU6: return x < 0.f ? 0.f : (x > 6.f ? 6.f : x);
     case A_SOFTPLUS: return x * a > 20.f ? x : log1pf(__expf(a * x)) / a;
     case A_SOFTSIGN: return x / (1.f + fabsf(x));
-    case A_HARDTANH: return fminf(fmaxf(x, a), b);
-    case A_HARDSIGMOID: return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f);
+    case A_HARDTANH: return x < a ? a : (x > b ? b : x);
+    case A_HARDSIGMOID: { const float t = 0.2f * x + 0.5f; return t < 0.f ? 0.f : (t > 1.f ? 1.f : t); }
     case A_LOGSIGMOID: return fminf(x, 0.f) - log1pf(__expf(-fabsf(x)));
     case A_TANHSHRINK: return x - tanhf(x);
     case A_SOFTSHRINK: return x > a ? x - a : (x < -a ? x + a : 0.f);
     case A_HARDSHRINK: return (x > a || x < -a) ? x : 0.f;
-    case A_THRESHOLD: return x > a ? x : b;
+    case A_THRESHOLD: return x <= a ? b : x;
     case A_EXP: return __expf(x);
     case A_LOG: return __logf(x);
     case A_SQRT: return sqrtf(x);
@@ -111,8 +113,8 @@ __device__ __forceinline__ void st1(void* p, long i, float v) {
 }
 
 template <bool BF>
-__global__ void act_fwd_kernel(const void* __restrict__ x, void* __restrict__ y, long n, int k, float a, float b) {
-  const long n8 = n >> 3;
+__global__ void act_fwd_kernel(const void* __restrict__ x, void* __restrict__ y, long n, long n8, int k, float a,
+                               float b) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     float v[8];
     ld8<BF>(x, i, v);
@@ -126,8 +128,7 @@ __global__ void act_fwd_kernel(const void* __restrict__ x, void* __restrict__ y,
 
 template <bool BF>
 __global__ void act_bwd_kernel(const void* __restrict__ x, const void* __restrict__ y, const void* __restrict__ dy,
-                               void* __restrict__ dx, long n, int k, float a, float b) {
-  const long n8 = n >> 3;
+                               void* __restrict__ dx, long n, long n8, int k, float a, float b) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     float xv[8], yv[8], gv[8];
     ld8<BF>(x, i, xv);
@@ -141,10 +142,17 @@ __global__ void act_bwd_kernel(const void* __restrict__ x, const void* __restric
     st1<BF>(dx, i, ld1<BF>(dy, i) * act_df(k, ld1<BF>(x, i), ld1<BF>(y, i), a, b));
 }
 
-int blocks_for(long n) {
-  long g = ((n >> 3) + 255) / 256;
+int blocks_for(long work) {
+  long g = (work + 255) / 256;
   if (g > 8192) g = 8192;
   return g < 1 ? 1 : (int)g;
+}
+
+// 16-byte granules of the vector body: all of them when every pointer is 16-byte aligned, none otherwise (a view at an
+// odd element offset inside a larger buffer then runs the scalar loop over the whole range)
+template <typename... P>
+long vec_granules(long n, P... ptrs) {
+  return ((reinterpret_cast<uintptr_t>(ptrs) | ...) & 15) == 0 ? n >> 3 : 0;
 }
 
 }  // namespace
@@ -153,8 +161,10 @@ extern "C" {
 
 int bigdl_act_fwd(const void* x, void* y, long n, int bf16, int kind, float a, float b, hipStream_t st) {
   if (kind < A_TANH || kind > A_ABS) return -1;
-  if (bf16) act_fwd_kernel<true><<<blocks_for(n), 256, 0, st>>>(x, y, n, kind, a, b);
-  else act_fwd_kernel<false><<<blocks_for(n), 256, 0, st>>>(x, y, n, kind, a, b);
+  const long n8 = vec_granules(n, x, y);
+  const int g = blocks_for(n8 ? n8 : n);
+  if (bf16) act_fwd_kernel<true><<<g, 256, 0, st>>>(x, y, n, n8, kind, a, b);
+  else act_fwd_kernel<false><<<g, 256, 0, st>>>(x, y, n, n8, kind, a, b);
   HIP_LAUNCH_CHECK();
   return 0;
 }
@@ -162,8 +172,10 @@ int bigdl_act_fwd(const void* x, void* y, long n, int bf16, int kind, float a, f
 int bigdl_act_bwd(const void* x, const void* y, const void* dy, void* dx, long n, int bf16, int kind, float a,
                   float b, hipStream_t st) {
   if (kind < A_TANH || kind > A_ABS) return -1;
-  if (bf16) act_bwd_kernel<true><<<blocks_for(n), 256, 0, st>>>(x, y, dy, dx, n, kind, a, b);
-  else act_bwd_kernel<false><<<blocks_for(n), 256, 0, st>>>(x, y, dy, dx, n, kind, a, b);
+  const long n8 = vec_granules(n, x, y, dy, dx);
+  const int g = blocks_for(n8 ? n8 : n);
+  if (bf16) act_bwd_kernel<true><<<g, 256, 0, st>>>(x, y, dy, dx, n, n8, kind, a, b);
+  else act_bwd_kernel<false><<<g, 256, 0, st>>>(x, y, dy, dx, n, n8, kind, a, b);
   HIP_LAUNCH_CHECK();
   return 0;
 }

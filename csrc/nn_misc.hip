@@ -118,8 +118,9 @@ __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, long 
 
 // ------------------------------------------------------------------------------------------ embedding
 // out[r, :] = W[idx[r], :] (idx < 0 -> paddingValue row of zeros)
+// vec: the host found D % 4 == 0 and both W and out 16-byte aligned (every row then is), so rows move as float4
 __global__ void embedding_fwd_kernel(const float* __restrict__ W, const long* __restrict__ idx, float* __restrict__ out,
-                                     long rows, int D, long nIndex) {
+                                     long rows, int D, long nIndex, int vec) {
   const int lane = threadIdx.x & 63;
   const long wid = (blockIdx.x * (long)blockDim.x + threadIdx.x) >> 6;
   const long nw = ((long)gridDim.x * blockDim.x) >> 6;
@@ -131,7 +132,7 @@ __global__ void embedding_fwd_kernel(const float* __restrict__ W, const long* __
       continue;
     }
     const float* w = W + k * D;
-    if ((D & 3) == 0) {
+    if (vec) {
       const float4* w4 = (const float4*)w;
       float4* o4 = (float4*)o;
       for (int d = lane; d < (D >> 2); d += 64) o4[d] = w4[d];
@@ -163,7 +164,7 @@ __device__ __forceinline__ long emb_id(const ID* ids, long r) { return (long)ids
 
 template <typename ID>
 __global__ void embedding_fwd_ids_kernel(const float* __restrict__ W, const ID* __restrict__ ids, float* __restrict__ out,
-                                         long rows, int D, long nIndex, int mask_zero) {
+                                         long rows, int D, long nIndex, int mask_zero, int vec) {
   const int lane = threadIdx.x & 63;
   const long wid = (blockIdx.x * (long)blockDim.x + threadIdx.x) >> 6;
   const long nw = ((long)gridDim.x * blockDim.x) >> 6;
@@ -176,7 +177,7 @@ __global__ void embedding_fwd_ids_kernel(const float* __restrict__ W, const ID* 
       continue;
     }
     const float* w = W + k * D;
-    if ((D & 3) == 0) {
+    if (vec) {
       for (int d = lane; d < (D >> 2); d += 64) reinterpret_cast<float4*>(o)[d] = reinterpret_cast<const float4*>(w)[d];
     } else {
       for (int d = lane; d < D; d += 64) o[d] = w[d];
@@ -234,7 +235,10 @@ __global__ void embedding_bwd_sorted_kernel(const void* __restrict__ gout, const
 
 // ------------------------------------------------------------------------------------------ bilinear resize (NCHW)
 // TF legacy mapping src = dst * scale, scale = in/out (align_corners: (in-1)/(out-1)), clamped at the edge.
+// No FMA contraction here: s is the rounded product in both directions. Contracted, f = fma(o, scale, -i0) differs from
+// s - i0 by up to half an ulp of s (3e-5 at s ~ 1000), and the backward's weights no longer are the forward's.
 __device__ __forceinline__ void bil_src(int o, int in, float scale, int& i0, int& i1, float& f) {
+#pragma clang fp contract(off)
   const float s = o * scale;
   i0 = (int)floorf(s);
   i0 = i0 < in - 1 ? i0 : in - 1;
@@ -357,18 +361,24 @@ void bigdl_dropout(const void* x, void* y, int is_bf16, long n, float p, float m
     dropout_kernel<float><<<blocks_for(n4), 256, 0, st>>>((const float*)x, (float*)y, n, p, mul, seed);
   HIP_LAUNCH_CHECK();
 }
+// float4 rows only where every row of W and out starts on a 16-byte boundary: a LookupTable weight is a view inside the
+// flat fp32 master vector, at any element offset
+static int emb_vec(const float* W, const float* out, int D) {
+  return (D & 3) == 0 && ((reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+}
 void bigdl_embedding_fwd(const float* W, const long* idx, float* out, long rows, int D, long nIndex, hipStream_t st) {
-  embedding_fwd_kernel<<<blocks_for(rows * 64), 256, 0, st>>>(W, idx, out, rows, D, nIndex);
+  embedding_fwd_kernel<<<blocks_for(rows * 64), 256, 0, st>>>(W, idx, out, rows, D, nIndex, emb_vec(W, out, D));
   HIP_LAUNCH_CHECK();
 }
 void bigdl_embedding_fwd_ids(const float* W, const void* ids, int ids_long, float* out, long rows, int D, long nIndex,
                              int mask_zero, hipStream_t st) {
+  const int vec = emb_vec(W, out, D);
   if (ids_long)
     embedding_fwd_ids_kernel<long><<<blocks_for(rows * 64), 256, 0, st>>>(W, (const long*)ids, out, rows, D, nIndex,
-                                                                          mask_zero);
+                                                                          mask_zero, vec);
   else
     embedding_fwd_ids_kernel<float><<<blocks_for(rows * 64), 256, 0, st>>>(W, (const float*)ids, out, rows, D, nIndex,
-                                                                           mask_zero);
+                                                                           mask_zero, vec);
   HIP_LAUNCH_CHECK();
 }
 void bigdl_embedding_bwd_ids(const void* gout, int gout_bf16, const void* ids, int ids_long, float* gW, long rows, int D,
