@@ -9,7 +9,9 @@ whole batch of trees is evaluated level-synchronously: all leaves in one GEMM, t
 every composer node of every tree in the batch whose children are ready, so the number of kernel launches is
 O(tree height) instead of O(nodes). The gate weights of the five composer gates are stacked into one
 (5H x H) matrix per child, so each level is two GEMMs + one fused pointwise pass. Backward is torch autograd
-over the same level schedule.
+over the same level schedule. With the fused route on (ops/tree_lstm.py: BIGDL_TREELSTM_FUSED, Engine property
+bigdl.treelstm.fused, set_fused) a level is ONE HIP launch per direction (csrc/treelstm.hip) and the backward is the
+explicit level sweep; the loop here stays the CPU path and the fallback.
 
 Tree encoding (TensorTree): ``trees`` is (batch, nodes, k); row n = [child_1, child_2, ..., tag] with 1-based
 child node indices (0 = none), last column = -1 for the root or the 1-based leaf (word) index for leaves;
@@ -145,6 +147,13 @@ class BinaryTreeLSTM(TreeLSTM):
 
     def fn(self, x):
         inputs, trees = x[1], x[2]
+        from ..ops import tree_lstm as fused
+
+        # GPU engine with the fused route on: one HIP launch per level and direction (ops/tree_lstm.py); a batch
+        # whose trees do not validate (a shared child, no single root) stays on the loop below
+        out = fused.forward(self, inputs, trees)
+        if out is not None:
+            return out
         B, N = trees.shape[0], trees.shape[1]
         H = self.hiddenSize
         dev = inputs.device

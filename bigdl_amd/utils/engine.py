@@ -187,6 +187,10 @@ class _Engine:
             from ..nn import recurrent
 
             recurrent.set_convlstm3d_fused(v)
+        elif k == "bigdl.treelstm.fused":           # BinaryTreeLSTM on the fused level kernels
+            from ..ops import tree_lstm
+
+            tree_lstm.set_fused(v)
         elif k == "bigdl.module.deviceTiming":      # getTimes in device time (HIP events) for GPU modules
             from ..nn import abstractnn
 

@@ -1933,6 +1933,126 @@ void convlstm_peep_wgrad(const Tensor& dg16, const Tensor& cs, const OptT& c0, c
   TORCH_CHECK(rc == 0, fn, ": unsupported arguments");
 }
 
+// ------------------------------------------------------------------------------------------ fused BinaryTreeLSTM levels
+// Host schedule of a batch of trees [B, N, 3] (int64, CPU) over inputs of L words: (tab int32 CPU, meta) as
+// bigdl_treelstm_schedule lays them out; an empty meta says the batch does not validate (the caller keeps its loop).
+std::tuple<Tensor, std::vector<int64_t>> treelstm_schedule(const Tensor& trees, int64_t L) {
+  TORCH_CHECK(!trees.is_cuda() && trees.scalar_type() == at::kLong && trees.dim() == 3 && trees.size(2) == 3 &&
+              trees.is_contiguous(), "treelstm_schedule: trees must be a contiguous int64 CPU tensor [B, N, 3]");
+  std::vector<int32_t> tab;
+  std::vector<int64_t> meta;
+  const bool fits = trees.size(0) < (1 << 30) && trees.size(1) < (1 << 30) && L >= 1 && L < (1 << 30);
+  if (!fits || bigdl_treelstm_schedule(trees.data_ptr<int64_t>(), (int)trees.size(0), (int)trees.size(1), (int)L, tab,
+                                       meta) != 0)
+    return {at::empty({0}, at::kInt), {}};
+  Tensor t = at::empty({(int64_t)tab.size()}, at::kInt);
+  std::copy(tab.begin(), tab.end(), t.data_ptr<int32_t>());
+  return {t, meta};
+}
+// The rows [start, start + rows) of the uploaded table; rows is a whole number of 16-row tiles.
+const int* treelstm_rows(const char* fn, const Tensor& tab, int64_t start, int64_t rows) {
+  check(tab, at::kInt, "tab");
+  TORCH_CHECK(tab.is_contiguous() && start >= 0 && rows > 0 && rows % 16 == 0 && (start + rows) * 8 <= tab.numel() &&
+              rows < (1 << 30), fn, ": rows outside the table");
+  return (const int*)tab.data_ptr() + start * 8;
+}
+// A slot buffer [slots >= need][width], contiguous.
+void treelstm_slots(const char* fn, const Tensor& t, int64_t need, int64_t width, const char* n) {
+  TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.size(0) >= need && t.size(1) == width, fn, ": ", n,
+              " must be contiguous [>= ", need, ", ", width, "]");
+}
+void treelstm_gather_x(const Tensor& x, const Tensor& tab, int64_t start, int64_t rows, const Tensor& xl16,
+                       int64_t leaves) {
+  const char* fn = "treelstm_gather_x";
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), fn, ": x must be contiguous [B * L, I]");
+  const int64_t I = x.size(1), Ip = (I + 31) / 32 * 32;
+  treelstm_slots(fn, xl16, leaves, Ip, "xl16");
+  const int rc = bigdl_treelstm_gather_x(cf(x, "x"), treelstm_rows(fn, tab, start, rows), (int)rows, mbf(xl16, "xl16"),
+                                         (int)I, (int)Ip, stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported arguments");
+}
+// One level forward. src16 / acts hold `slots` rows the level may read or write by its own slot (leaves, or composer
+// slots + the zero slot); cch / hch16 [>= Z + 1, 2 Hp] are written at the parents' slots; out [B * N, H].
+void treelstm_fwd_level(const Tensor& W16, const Tensor& src16, const Tensor& bias, const Tensor& tab, int64_t start,
+                        int64_t rows, const Tensor& cch, const Tensor& hch16, const Tensor& out, const Tensor& acts,
+                        int64_t slots, int64_t Z, bool leaf) {
+  const char* fn = "treelstm_fwd_level";
+  TORCH_CHECK(out.dim() == 2 && out.is_contiguous() && cch.dim() == 2 && cch.size(1) % 64 == 0, fn,
+              ": out [B * N, H] contiguous, cch [slots, 2 Hp]");
+  const int64_t H = out.size(1), Hp = cch.size(1) / 2;
+  TORCH_CHECK(H >= 1 && Hp == (H + 31) / 32 * 32 && Z >= 0 && slots >= 1, fn, ": Hp must be H rounded up to 32");
+  TORCH_CHECK(W16.dim() == 2 && W16.is_contiguous() && W16.size(0) % Hp == 0 && W16.size(1) % 32 == 0, fn,
+              ": W16 must be contiguous [ng * Hp, K]");
+  const int64_t ng = W16.size(0) / Hp, K = W16.size(1);
+  TORCH_CHECK(leaf || K == 2 * Hp, fn, ": a composer level has K = 2 Hp");
+  TORCH_CHECK(bias.is_contiguous() && bias.numel() == ng * Hp, fn, ": bias must be the packed [Hp * ng] vector");
+  treelstm_slots(fn, src16, slots, K, "src16");
+  treelstm_slots(fn, acts, slots, (leaf ? ng : ng + 1) * Hp, "acts");
+  treelstm_slots(fn, cch, Z + 1, 2 * Hp, "cch");
+  treelstm_slots(fn, hch16, Z + 1, 2 * Hp, "hch16");
+  TORCH_CHECK(leaf || slots >= Z + 1, fn, ": composer levels read the zero slot");
+  const int rc = bigdl_treelstm_fwd_level(cbf(W16, "W16"), cbf(src16, "src16"), cf(bias, "bias"),
+                                          treelstm_rows(fn, tab, start, rows), (int)rows, mf(cch, "cch"),
+                                          mbf(hch16, "hch16"), mf(out, "out"), mf(acts, "acts"), (int)H, (int)Hp, (int)K,
+                                          (int)Z, (int)ng, leaf ? 1 : 0, stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported arguments");
+}
+// One level backward; split = rows of the level (from its start) that hang on the left. dg16p / dcp / cch are the
+// composers' slot buffers [>= Z + 1, .]; acts / dg / dg16 the level's own (`slots` rows: leaves, or the composers').
+void treelstm_bwd_level(const Tensor& WT16, const Tensor& dg16p, const Tensor& gout, const Tensor& tab, int64_t start,
+                        int64_t split, int64_t rows, const Tensor& acts, const Tensor& cch, const Tensor& dcp,
+                        const Tensor& dg, const Tensor& dg16, int64_t slots, int64_t Z, bool gate_output, bool leaf) {
+  const char* fn = "treelstm_bwd_level";
+  TORCH_CHECK(gout.dim() == 2 && gout.is_contiguous() && dcp.dim() == 2 && dcp.size(1) % 64 == 0, fn,
+              ": gout [B * N, H] contiguous, dcp [slots, 2 Hp]");
+  const int64_t H = gout.size(1), Hp = dcp.size(1) / 2, ngp = gate_output ? 5 : 4, K = ngp * Hp;
+  const int64_t ng = leaf ? (gate_output ? 2 : 1) : ngp;
+  TORCH_CHECK(H >= 1 && Hp == (H + 31) / 32 * 32 && Z >= 0 && slots >= 1, fn, ": Hp must be H rounded up to 32");
+  TORCH_CHECK(WT16.dim() == 3 && WT16.is_contiguous() && WT16.size(0) == 2 && WT16.size(1) == Hp && WT16.size(2) == K, fn,
+              ": WT16 must be contiguous [2, Hp, ng * Hp]");
+  treelstm_slots(fn, dg16p, Z + 1, K, "dg16p");
+  treelstm_slots(fn, dcp, Z + 1, 2 * Hp, "dcp");
+  treelstm_slots(fn, cch, Z + 1, 2 * Hp, "cch");
+  treelstm_slots(fn, acts, slots, (leaf ? ng : ng + 1) * Hp, "acts");
+  treelstm_slots(fn, dg, slots, ng * Hp, "dg");
+  treelstm_slots(fn, dg16, slots, ng * Hp, "dg16");
+  TORCH_CHECK(leaf || slots >= Z + 1, fn, ": composer levels read the zero slot");
+  TORCH_CHECK(split >= 0 && split <= rows && split % 16 == 0, fn, ": split must be a tile boundary of the level");
+  const int rc = bigdl_treelstm_bwd_level(cbf(WT16, "WT16"), cbf(dg16p, "dg16p"), cf(gout, "gout"),
+                                          treelstm_rows(fn, tab, start, rows), (int)split, (int)rows, cf(acts, "acts"),
+                                          cf(cch, "cch"), mf(dcp, "dcp"), mf(dg, "dg"), mbf(dg16, "dg16"), (int)H,
+                                          (int)Hp, (int)K, (int)Z, gate_output ? 1 : 0, leaf ? 1 : 0, stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported arguments");
+}
+// Column sums of the fp32 gate gradients a [R, C] in a fixed order (the bias gradients).
+Tensor treelstm_colsum(const Tensor& a) {
+  const char* fn = "treelstm_colsum";
+  TORCH_CHECK(a.dim() == 2 && a.is_contiguous() && a.size(0) >= 1 && a.size(1) >= 1 && a.size(0) < (1 << 30) &&
+              a.size(1) < (1 << 30), fn, ": a must be contiguous [R, C]");
+  const int R = (int)a.size(0), C = (int)a.size(1);
+  Tensor part = at::empty({bigdl_treelstm_colsum_ws(R, C)}, a.options());
+  Tensor out = at::empty({C}, a.options());
+  const int rc = bigdl_treelstm_colsum(cf(a, "a"), mf(part, "part"), mf(out, "out"), R, C, stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported arguments");
+  return out;
+}
+// gin [B * L, I] from dxl [leaf slots, Ip] and the table's word lists (off at tab[off0], items at tab[items0]).
+void treelstm_leaf_dx(const Tensor& dxl, const Tensor& tab, int64_t off0, int64_t items0, const Tensor& gin,
+                      int64_t leaves) {
+  const char* fn = "treelstm_leaf_dx";
+  check(tab, at::kInt, "tab");
+  TORCH_CHECK(gin.dim() == 2 && gin.is_contiguous() && gin.size(0) >= 1 && gin.size(0) < (1 << 30), fn,
+              ": gin must be contiguous [B * L, I]");
+  const int64_t words = gin.size(0), I = gin.size(1), Ip = (I + 31) / 32 * 32;
+  treelstm_slots(fn, dxl, leaves, Ip, "dxl");
+  TORCH_CHECK(tab.is_contiguous() && off0 >= 0 && items0 == off0 + words + 1 && items0 + leaves <= tab.numel(), fn,
+              ": word lists outside the table");
+  const int* t = (const int*)tab.data_ptr();
+  const int rc = bigdl_treelstm_leaf_dx(cf(dxl, "dxl"), t + off0, t + items0, mf(gin, "gin"), (int)words, (int)I, (int)Ip,
+                                        stream());
+  TORCH_CHECK(rc == 0, fn, ": unsupported arguments");
+}
+
 // Whole-sequence persistent GRU (csrc/lstm_seq.hip): Wrz16 [2H, H], Wn16 [H, H] bf16; xg [B, T, 3H] f32 (r|z|n),
 // h16 [T + 1, B, H] bf16 (h16[0] = h0), rh16 [T, B, H] bf16, gates [3, T, B, H] f32, out [B, T, H] f32.
 bool gru_seq_supported(int64_t B, int64_t H) { return bigdl_gru_seq_supported((int)B, (int)H) != 0; }
@@ -2485,6 +2605,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pI") = py::none(), py::arg("pF") = py::none(), py::arg("pO") = py::none(), py::arg("hard") = false);
   m.def("convlstm_peep_wgrad_slices", &convlstm_peep_wgrad_slices);
   m.def("convlstm_peep_wgrad", &convlstm_peep_wgrad);
+  m.def("treelstm_schedule", &treelstm_schedule, py::arg("trees"), py::arg("L"));
+  m.def("treelstm_gather_x", &treelstm_gather_x, py::arg("x"), py::arg("tab"), py::arg("start"), py::arg("rows"),
+        py::arg("xl16"), py::arg("leaves"));
+  m.def("treelstm_fwd_level", &treelstm_fwd_level, py::arg("W16"), py::arg("src16"), py::arg("bias"), py::arg("tab"),
+        py::arg("start"), py::arg("rows"), py::arg("cch"), py::arg("hch16"), py::arg("out"), py::arg("acts"),
+        py::arg("slots"), py::arg("Z"), py::arg("leaf"));
+  m.def("treelstm_bwd_level", &treelstm_bwd_level, py::arg("WT16"), py::arg("dg16p"), py::arg("gout"), py::arg("tab"),
+        py::arg("start"), py::arg("split"), py::arg("rows"), py::arg("acts"), py::arg("cch"), py::arg("dcp"),
+        py::arg("dg"), py::arg("dg16"), py::arg("slots"), py::arg("Z"), py::arg("gate_output"), py::arg("leaf"));
+  m.def("treelstm_colsum", &treelstm_colsum, py::arg("a"));
+  m.def("treelstm_leaf_dx", &treelstm_leaf_dx, py::arg("dxl"), py::arg("tab"), py::arg("off0"), py::arg("items0"),
+        py::arg("gin"), py::arg("leaves"));
   m.def("lstm_seq_supported", &lstm_seq_supported);
   m.def("set_lstm_seq", &bigdl_set_lstm_seq);
   m.def("lstm_seq_sync_words", &lstm_seq_sync_words);

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #define CONV_MAX_TAPS 64
 // Implicit-GEMM "NT" convolution launch (forward, or one stride phase of the data gradient):
 //   out[orow(m)][n] = sum_{t < ntaps, c < Cs} src[pix(m) + (o_h*mul_h + tap_h[t], o_w*mul_w + tap_w[t])][c]
@@ -614,6 +616,39 @@ int bigdl_convlstm3d_bwd_step(const uint16_t* UT, const uint16_t* dg_next, const
                               const float* acts, const float* c_prev, const float* c_t, float* dc, uint16_t* dg_out,
                               const float* pI, const float* pF, const float* pO, int hard, int B, int C, int D, int H,
                               int W, int k, hipStream_t st);
+// Fused BinaryTreeLSTM levels (csrc/treelstm.hip): one launch per tree level and direction; the file's header gives the
+// slot-major layout. Hp / Ip = hidden / input width rounded up to 32, ng = 5 gate blocks (4 without the output gate),
+// leaves 2 (1). Every launch entry returns -1 without a launch on an unsupported argument.
+// Schedule (host only): walks trees [B][N][3] (int64: left, right, tag; 1-based children, 0 = none, left == -1 marks a
+// padding row, tag == -1 the root, else the 1-based word of a leaf) from each root with an explicit stack. Returns -1
+// unless every tree has one root, every child index is in range and every reachable node has exactly one parent (the
+// kernels' plain stores rest on that). tab = [rows][8] ints (node row b * N + n or -1 for tile padding, own slot, parent
+// slot, side, input row b * L + word, 3 unused), level by level from the leaves, each level as [left children | right
+// children] with both groups padded to 16 rows; then off [B * L + 1] and items [leaves]: the leaf slots naming each
+// input row. meta = {composer slots S (the zero slot Z = S), leaves, levels, rows, offset of off in tab, offset of
+// items, then (start, split, end) rows of every level}.
+int bigdl_treelstm_schedule(const int64_t* trees, int B, int N, int L, std::vector<int32_t>& tab,
+                            std::vector<int64_t>& meta);
+// xl16 [leaf slot][Ip] bf16 = input rows x [B * L][I] gathered by the leaf level's table rows, zero-padded.
+int bigdl_treelstm_gather_x(const float* x, const int* tab, int rows, uint16_t* xl16, int I, int Ip, hipStream_t st);
+// Forward of one level (tab = that level's first row, rows % 16 == 0). W16 [ng * Hp][K] bf16 with row = unit * ng + gate,
+// bias [Hp * ng] packed alike; src16 [slot][K] bf16: hch16 (K = 2 Hp) for composers, xl16 (K = Ip) for leaves. Writes
+// out [B * N][H], acts at the own slot, and c / bf16 h into the parent's slot of cch / hch16 [slot][2 Hp].
+int bigdl_treelstm_fwd_level(const uint16_t* W16, const uint16_t* src16, const float* bias, const int* tab, int rows,
+                             float* cch, uint16_t* hch16, float* out, float* acts, int H, int Hp, int K, int Z, int ng,
+                             int leaf, hipStream_t st);
+// Backward of one level: dh = gout[node] + dg16p[parent slot] . W_side (WT16 [2][Hp][K], K = ng * Hp gate-major), the cell
+// backward, dg / dg16 at the own slot (composer [slot][ng * Hp], leaf [slot][nl * Hp]) and dcp [slot][2 Hp] = dc * lf,
+// dc * rf for the children. Rows [0, split) hang on the left of their parents.
+int bigdl_treelstm_bwd_level(const uint16_t* WT16, const uint16_t* dg16p, const float* gout, const int* tab, int split,
+                             int rows, const float* acts, const float* cch, float* dcp, float* dg, uint16_t* dg16,
+                             int H, int Hp, int K, int Z, int gate_output, int leaf, hipStream_t st);
+// out [C] = column sums of a [R][C] in a fixed order; part = workspace of bigdl_treelstm_colsum_ws(R, C) floats.
+long bigdl_treelstm_colsum_ws(int R, int C);
+int bigdl_treelstm_colsum(const float* a, float* part, float* out, int R, int C, hipStream_t st);
+// gin [words][I] = per input row, the sum of dxl [leaf slot][Ip] over the leaves naming it (off / items of the schedule).
+int bigdl_treelstm_leaf_dx(const float* dxl, const int* off, const int* items, float* gin, int words, int I, int Ip,
+                           hipStream_t st);
 // Whole-sequence persistent LSTM (csrc/lstm_seq.hip): one launch per direction, W resident in VGPRs.
 int bigdl_lstm_seq_supported(int B, int H);
 void bigdl_set_lstm_seq(int v);
