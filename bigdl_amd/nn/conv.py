@@ -571,10 +571,10 @@ class SpatialSeparableConvolution(AutogradModule):
     def fn(self, x):
         if self.dataFormat == "NHWC":
             x = x.permute(0, 3, 1, 2)
-        # depthwise half on the direct grouped kernel, pointwise half on the MFMA GEMM
-        y = conv_fn.group_conv2d(x.to(self.depthWeight.dtype), self.depthWeight, None, self.s, self.p,
-                                 groups=self.cin)
-        y = conv_fn.conv2d(y, self.pointWeight, self.bias)        # pointwise half on the MFMA GEMM
+        # GPU: depthwise half on the direct grouped kernel and pointwise half on the MFMA GEMM, or both in one launch
+        # (csrc/sepconv.hip) when the fused route is switched on and takes the geometry
+        y = conv_fn.separable_conv2d(x.to(self.depthWeight.dtype), self.depthWeight, self.pointWeight, self.bias,
+                                     self.s, self.p)
         return y.permute(0, 2, 3, 1) if self.dataFormat == "NHWC" else y
 
 

@@ -10,6 +10,7 @@ bf16 NHWC with channels zero-padded to multiples of 8 (the kernels' 16-byte gran
     conv_transpose2d(x, w, b, stride, pad, adj) y = x (*)^T w      fwd: the dgrad kernel, bwd: fwd + wgrad
     conv3d(x, w, b, stride, pad)                native 3-D implicit GEMM (csrc/conv3d.hip), one launch per direction
     conv_transpose3d(x, w, b, stride, pad, adj) fwd: the 3-D dgrad kernel, bwd: 3-D fwd + wgrad
+    separable_conv2d(x, wd, wp, b, stride, pad) depthwise + pointwise; fused forward (csrc/sepconv.hip) when switched on
 
 The 3-D functions run bf16 NDHWC operands with fp32 results (every tap accumulated in fp32, nothing rounded to bf16
 afterwards); the weight gradient's voxel splits are summed in fixed order, so it is deterministic.
@@ -211,6 +212,106 @@ def group_conv2d(x, w, b=None, stride=(1, 1), pad=(0, 0), dil=(1, 1), groups=1):
     outs = [conv2d(x[:, g * cin_g:(g + 1) * cin_g], w[g * cout_g:(g + 1) * cout_g],
                    b[g * cout_g:(g + 1) * cout_g] if b is not None else None, stride, pad, dil) for g in range(groups)]
     return torch.cat(outs, 1)
+
+
+# The fused depthwise-separable forward (csrc/sepconv.hip) is opt-in: BIGDL_SEPCONV_FUSED=1, set_sepconv_fused, or the
+# Engine property bigdl.sepconv.fused. Unset means DEFAULT_SEPCONV_FUSED (the depthwise kernel + the pointwise GEMM).
+DEFAULT_SEPCONV_FUSED = False
+_SEPCONV_FUSED = [None]
+_SEPARABLE_ROUTE = [None]
+
+
+def set_sepconv_fused(v):
+    """True / False, "1" / "0", or None for the default."""
+    _SEPCONV_FUSED[0] = None if v is None or v == "" else str(v).lower() in ("1", "true", "yes")
+
+
+def sepconv_fused():
+    v = _SEPCONV_FUSED[0]
+    if v is None:
+        env = os.environ.get("BIGDL_SEPCONV_FUSED", "")
+        v = DEFAULT_SEPCONV_FUSED if env == "" else env.lower() in ("1", "true", "yes")
+    return bool(v)
+
+
+def last_separable_route():
+    """"fused" or "split": what the last separable_conv2d call on the GPU ran (None before the first)."""
+    return _SEPARABLE_ROUTE[0]
+
+
+class _SepConv(torch.autograd.Function):
+    """Depthwise + pointwise convolution, forward in ONE launch (csrc/sepconv.hip): the depthwise result lives in LDS
+    and feeds the pointwise MFMA GEMM. Training keeps its bf16 NHWC rounding (mid16, written by the same launch) for the
+    pointwise weight gradient; the backward runs the kernels of the two-kernel path on it."""
+
+    @staticmethod
+    def forward(ctx, x, wd, wp, b, stride, pad):
+        from . import native
+
+        x, wd = x.float().contiguous(), wd.float().contiguous()
+        N, Cin, H, W = x.shape
+        Cmid, K = wd.shape[0], wp.shape[0]
+        C8, K8, C32 = _p8(Cmid), _p8(K), -(-Cmid // 32) * 32
+        OH = _out_size(H, wd.shape[2], stride[0], pad[0], 1)
+        OW = _out_size(W, wd.shape[3], stride[1], pad[1], 1)
+        wp32 = _zeros(K8, C32, dtype=BF16, device=x.device)
+        wp32[:K, :Cmid].copy_(wp.reshape(K, Cmid))
+        y = x.new_empty(N, K, OH, OW)
+        train = any(ctx.needs_input_grad[:4])
+        mid16 = torch.empty(N, OH, OW, C8, dtype=BF16, device=x.device) if train else None
+        native.get().sepconv_fwd(x, wd, wp32, b.float().contiguous() if b is not None else None, y, mid16,
+                                 [stride[0], stride[1], pad[0], pad[1]])
+        if train:
+            ctx.save_for_backward(x, wd, _w16(wp, K8, C8), mid16)
+        ctx.geo = (stride, pad, K, Cmid, b is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import native
+
+        x, wd, w16, mid16 = ctx.saved_tensors
+        stride, pad, K, Cmid, has_b = ctx.geo
+        K8, C8 = w16.shape[0], w16.shape[1]
+        N, OH, OW, _ = mid16.shape
+        gy16 = _act16(gy, K8)
+        gx = gwd = gwp = gb = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gm = cv.conv2d_dgrad(gy16, cv.transpose_w(w16), (N, C8, OH, OW), (1, 1), (0, 0))
+            gm = gm[:, :Cmid].float().contiguous()
+            geo = [stride[0], stride[1], pad[0], pad[1], 1, 1, x.shape[1]]
+            if ctx.needs_input_grad[0]:
+                gx = torch.empty_like(x)
+                native.get().gconv(1, gx, wd, None, gm, geo)
+            if ctx.needs_input_grad[1]:
+                gwd = torch.zeros_like(wd)
+                native.get().gconv(2, x, gwd, None, gm, geo)
+        if ctx.needs_input_grad[2] or (has_b and ctx.needs_input_grad[3]):
+            dw = _zeros(w16.shape, device=gy.device, memory_format=CL)
+            db = _zeros(K8, device=gy.device) if has_b else None
+            cv.conv2d_wgrad(gy16, mid16.permute(0, 3, 1, 2), dw, db, (1, 1), (0, 0))
+            gwp = dw[:K, :Cmid].contiguous()
+            gb = db[:K] if has_b else None
+        return gx, gwd, gwp, gb, None, None
+
+
+def separable_conv2d(x, depth_w, point_w, bias=None, stride=(1, 1), pad=(0, 0)):
+    """y = conv1x1(depthwise(x, depth_w), point_w) + bias; depth_w [Cin * dm, 1, kH, kW], point_w [Cout, Cin * dm, 1,
+    1]. GPU: the fused forward when it is switched on and takes the geometry (last_separable_route() == "fused"), else
+    the depthwise kernel followed by the pointwise GEMM ("split"). CPU engine: torch."""
+    cin = x.shape[1]
+    if not x.is_cuda:
+        return F.conv2d(F.conv2d(x, depth_w, None, stride, pad, 1, cin), point_w, bias)
+    if sepconv_fused() and depth_w.shape[1] == 1 and depth_w.shape[0] % cin == 0:
+        from . import native
+
+        N, _, H, W = x.shape
+        if native.get().sepconv_supported(N, cin, H, W, depth_w.shape[0] // cin, point_w.shape[0], depth_w.shape[2],
+                                          depth_w.shape[3], [stride[0], stride[1], pad[0], pad[1]]):
+            _SEPARABLE_ROUTE[0] = "fused"
+            return _SepConv.apply(x, depth_w, point_w, bias, tuple(stride), tuple(pad))
+    _SEPARABLE_ROUTE[0] = "split"
+    return conv2d(group_conv2d(x, depth_w, None, stride, pad, groups=cin), point_w, bias)
 
 
 def conv1d(x, w, b=None, stride=1):

@@ -191,6 +191,10 @@ class _Engine:
             from ..ops import tree_lstm
 
             tree_lstm.set_fused(v)
+        elif k == "bigdl.sepconv.fused":            # SpatialSeparableConvolution forward in one launch
+            from ..ops import conv_fn
+
+            conv_fn.set_sepconv_fused(v)
         elif k == "bigdl.module.deviceTiming":      # getTimes in device time (HIP events) for GPU modules
             from ..nn import abstractnn
 

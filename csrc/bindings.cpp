@@ -2320,6 +2320,49 @@ void gconv(int64_t pass, const Tensor& x_or_dx, const Tensor& w_or_dw, const Opt
   else { c.x = cf(x, "x"); c.dwt = mf(w, "dw"); c.db = omf(b_or_db, "db"); c.dy = cf(y, "dy"); }
   TORCH_CHECK(bigdl_gconv(&c, (int)pass, stream()) == 0, "gconv: bad geometry");
 }
+// Fused depthwise-separable convolution forward (csrc/sepconv.hip). x fp32 NCHW, wd fp32 [Cin * dm][1][kH][kW] (or
+// [Cin * dm][kH][kW]), wp bf16 [Cout8][Cmid32] zero-padded, y fp32 [N][Cout][OH][OW], mid16 (optional) bf16
+// [N][OH][OW][Cmid8]; geo = [sH, sW, pH, pW]. Every extent is read from the tensors.
+static SepConvGeo sepconv_geo(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t dm, int64_t Cout, int64_t kH,
+                              int64_t kW, const std::vector<int64_t>& geo, bool* ok) {
+  TORCH_CHECK(geo.size() == 4, "sepconv: geo = [sH, sW, pH, pW]");
+  const int64_t v[] = {N, Cin, H, W, dm, Cout, kH, kW, geo[0], geo[1], geo[2], geo[3]};
+  *ok = true;
+  for (int64_t e : v) *ok = *ok && e >= 0 && e < (1ll << 31);
+  SepConvGeo g{};
+  if (!*ok || geo[0] < 1 || geo[1] < 1) { *ok = false; return g; }
+  g.N = (int)N; g.Cin = (int)Cin; g.dm = (int)dm; g.H = (int)H; g.W = (int)W; g.Cout = (int)Cout;
+  g.kH = (int)kH; g.kW = (int)kW; g.sH = (int)geo[0]; g.sW = (int)geo[1]; g.pH = (int)geo[2]; g.pW = (int)geo[3];
+  g.OH = (int)((H + 2 * geo[2] - kH) / geo[0] + 1); g.OW = (int)((W + 2 * geo[3] - kW) / geo[1] + 1);
+  return g;
+}
+bool sepconv_supported(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t dm, int64_t Cout, int64_t kH, int64_t kW,
+                       std::vector<int64_t> geo) {
+  bool ok;
+  const SepConvGeo g = sepconv_geo(N, Cin, H, W, dm, Cout, kH, kW, geo, &ok);
+  return ok && bigdl_sepconv_supported(&g) == 1;
+}
+void sepconv_fwd(const Tensor& x, const Tensor& wd, const Tensor& wp, const OptT& bias, const Tensor& y,
+                 const OptT& mid16, std::vector<int64_t> geo) {
+  TORCH_CHECK(x.dim() == 4 && y.dim() == 4 && x.is_contiguous() && y.is_contiguous() && x.size(0) == y.size(0),
+              "sepconv_fwd: x / y must be contiguous NCHW tensors of one batch");
+  TORCH_CHECK((wd.dim() == 3 || (wd.dim() == 4 && wd.size(1) == 1)) && wd.is_contiguous() && x.size(1) > 0 &&
+              wd.size(0) > 0 && wd.size(0) % x.size(1) == 0, "sepconv_fwd: wd must be [Cin * dm][1][kH][kW]");
+  const int64_t Cmid = wd.size(0), Cout = y.size(1);
+  bool ok;
+  const SepConvGeo g = sepconv_geo(x.size(0), x.size(1), x.size(2), x.size(3), Cmid / x.size(1), Cout,
+                                   wd.size(wd.dim() - 2), wd.size(wd.dim() - 1), geo, &ok);
+  TORCH_CHECK(ok && bigdl_sepconv_supported(&g) == 1, "sepconv_fwd: unsupported geometry");
+  TORCH_CHECK(y.size(2) == g.OH && y.size(3) == g.OW, "sepconv_fwd: y must be [N][Cout][OH][OW]");
+  TORCH_CHECK(wp.dim() == 2 && wp.is_contiguous() && wp.size(0) == (Cout + 7) / 8 * 8 &&
+              wp.size(1) == (Cmid + 31) / 32 * 32, "sepconv_fwd: wp must be [Cout8][Cmid32]");
+  if (bias && bias->defined()) TORCH_CHECK(bias->numel() == Cout && bias->is_contiguous(), "sepconv_fwd: bias is [Cout]");
+  if (mid16 && mid16->defined())
+    TORCH_CHECK(mid16->is_contiguous() && mid16->dim() == 4 && mid16->size(0) == g.N && mid16->size(1) == g.OH &&
+                mid16->size(2) == g.OW && mid16->size(3) == (Cmid + 7) / 8 * 8, "sepconv_fwd: mid16 must be [N][OH][OW][Cmid8]");
+  TORCH_CHECK(bigdl_sepconv_fwd(cf(x, "x"), cf(wd, "wd"), cbf(wp, "wp"), ocf(bias, "bias"), mf(y, "y"),
+                                ombf(mid16, "mid16"), &g, stream()) == 0, "sepconv_fwd: launch refused");
+}
 // Volumetric convolution (csrc/conv3d.hip). x [N][T][H][W][C] and y [N][OT][OH][OW][K] are contiguous NDHWC tensors
 // of the convolution's input and output grids (bf16 as operands, fp32 as results), w is [K][kT][kH][kW][C] or, for the
 // data gradient, wt [C][kT][kH][kW][K]; geo = [sT, sH, sW, pT, pH, pW]. Every extent is read from the tensors, so
@@ -2637,6 +2680,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"), py::arg("H"),
         py::arg("causal"), py::arg("o"), py::arg("lse"), py::arg("mlog"), py::arg("drop_p") = 0.0, py::arg("seed") = 0);
   m.def("gconv", &gconv);
+  m.def("sepconv_fwd", &sepconv_fwd);
+  m.def("sepconv_supported", &sepconv_supported);
   m.def("conv3d_fwd", &conv3d_fwd);
   m.def("conv3d_dgrad", &conv3d_dgrad);
   m.def("conv3d_wgrad", &conv3d_wgrad);

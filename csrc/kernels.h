@@ -814,4 +814,16 @@ int bigdl_conv3d_wgrad_splits(const Conv3dArgs* g);
 int bigdl_conv3d_wgrad_split_min(void);
 int bigdl_conv3d_wgrad(const uint16_t* dy, const uint16_t* x, float* dw, float* db, float* ws, const Conv3dArgs* g,
                        hipStream_t st);
+
+// Fused depthwise-separable convolution forward (csrc/sepconv.hip): y = pointwise(depthwise(x)) + bias in one launch,
+// the depthwise result ("mid", Cmid = Cin * dm channels, mid channel m reads input channel m / dm) living only in LDS.
+// x fp32 [N][Cin][H][W], wd fp32 [Cmid][kH][kW], wp bf16 [Cout8][Cmid32] (rows and columns zero-padded to multiples of
+// 8 and 32), bias fp32 [Cout] or null, y fp32 [N][Cout][OH][OW]; mid16 (optional) bf16 [N][OH][OW][Cmid8], every
+// element written (padding channels as 0). bigdl_sepconv_supported: 1 when the kernel takes the geometry (kernel extents
+// 1..7, strides 1..2, 0 <= pad < kernel extent, consistent output size, LDS within the 160 KiB of a CU, extents within
+// 32-bit offsets); bigdl_sepconv_fwd returns -1 otherwise.
+typedef struct { int N, Cin, dm, H, W, Cout, OH, OW, kH, kW, sH, sW, pH, pW; } SepConvGeo;
+int bigdl_sepconv_supported(const SepConvGeo* g);
+int bigdl_sepconv_fwd(const float* x, const float* wd, const uint16_t* wp, const float* bias, float* y,
+                      uint16_t* mid16, const SepConvGeo* g, hipStream_t st);
 }
