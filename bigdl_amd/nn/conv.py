@@ -266,9 +266,26 @@ class SpatialConvolution(TensorModule):
     def _geo_g(self, ph, pw):
         return [self.strideH, self.strideW, ph, pw, self.dilationH, self.dilationW, self.nGroup]
 
+    def _mfma_groups(self, x, ph, pw):
+        """All groups in one MFMA launch per pass (csrc/gconv_mfma.hip): when the route is switched on
+        (ops/conv_fn.py set_gconv_mfma) and the kernels take the geometry. Records conv_fn.last_group_route()."""
+        return conv_fn.group_route(x.shape, self.weight.shape, (self.strideH, self.strideW), (ph, pw),
+                                   (self.dilationH, self.dilationW), self.nGroup) == "mfma"
+
     def _fwd_gpu_grouped(self, x, ph, pw):
         G = self.nGroup
         cin, cout = self.nInputPlane // G, self.nOutputPlane // G
+        if self._mfma_groups(x, ph, pw):
+            x16 = cv.to_nhwc_bf16(x)
+            self._x16 = x16
+            OH = cv.out_size(x.shape[2], self.kernelH, self.strideH, ph, self.dilationH)
+            OW = cv.out_size(x.shape[3], self.kernelW, self.strideW, pw, self.dilationW)
+            y = torch.empty((x.shape[0], self.nOutputPlane, OH, OW), dtype=BF16, device=x.device, memory_format=CL)
+            ops.native.get().gconv_mfma_fwd(x16, cv.weight_krsc_bf16(self.w16("weight")),
+                                            self.bias.float() if self.bias is not None else None, y,
+                                            bool(self.fuse_relu), self._geo_g(ph, pw))
+            self._geom = (x.shape, ph, pw)
+            return y
         if self._direct_groups():
             xf = x.float().contiguous()
             OH = cv.out_size(x.shape[2], self.kernelH, self.strideH, ph, self.dilationH)
@@ -377,6 +394,12 @@ class SpatialConvolution(TensorModule):
             return gi
         G = self.nGroup
         cin, cout = self.nInputPlane // G, self.nOutputPlane // G
+        if self._mfma_groups(x, ph, pw):
+            dx = torch.empty((x.shape[0], self.nInputPlane, x.shape[2], x.shape[3]), dtype=BF16, device=gy.device,
+                             memory_format=CL)
+            wt = conv_fn.group_transpose_w(cv.weight_krsc_bf16(self.w16("weight")), G)
+            ops.native.get().gconv_mfma_dgrad(gy16, wt, dx, self._geo_g(ph, pw))
+            return dx
         if self._direct_groups():
             gyf = gy.float().contiguous()
             dx = torch.empty(x.shape[0], self.nInputPlane, x.shape[2], x.shape[3], device=gy.device)
@@ -446,6 +469,12 @@ class SpatialConvolution(TensorModule):
             # gets it materialised on the weight-gradient stream
             pre = self._x16_pre
         st, pd, dl = (self.strideH, self.strideW), (ph, pw), (self.dilationH, self.dilationW)
+        if self.nGroup != 1 and self._mfma_groups(x, ph, pw):
+            dw, db = conv_fn.group_wgrad(gy16, x16, self.weight.shape, self._geo_g(ph, pw), self.bias is not None)
+            self.gradWeight.add_(dw, alpha=self.scaleW)
+            if db is not None:
+                self.gradBias.add_(db, alpha=self.scaleB)
+            return
         if self.nGroup != 1 and self._direct_groups():
             xf = getattr(self, "_xf", None)
             if xf is None or xf.shape != x.shape:

@@ -198,15 +198,123 @@ class _GroupConv(torch.autograd.Function):
         return gx, gw, gb, None, None, None, None
 
 
+# Grouped convolution on MFMA, every group in one launch per direction (csrc/gconv_mfma.hip), is opt-in:
+# BIGDL_GCONV_MFMA=1, set_gconv_mfma, or the Engine property bigdl.gconv.mfma. Unset means DEFAULT_GCONV_MFMA (the
+# direct kernel up to 16 input channels per group, else one implicit-GEMM convolution per group).
+DEFAULT_GCONV_MFMA = False
+_GCONV_MFMA = [None]
+_GROUP_ROUTE = [None]
+
+
+def set_gconv_mfma(v):
+    """True / False, "1" / "0", or None for the default."""
+    _GCONV_MFMA[0] = None if v is None or v == "" else str(v).lower() in ("1", "true", "yes")
+
+
+def gconv_mfma():
+    v = _GCONV_MFMA[0]
+    if v is None:
+        env = os.environ.get("BIGDL_GCONV_MFMA", "")
+        v = DEFAULT_GCONV_MFMA if env == "" else env.lower() in ("1", "true", "yes")
+    return bool(v)
+
+
+def last_group_route():
+    """"mfma", "direct" or "loop": what the last grouped convolution on the GPU ran (None before the first)."""
+    return _GROUP_ROUTE[0]
+
+
+def group_geo(stride, pad, dil, groups):
+    return [stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], groups]
+
+
+def group_route(xshape, wshape, stride, pad, dil, groups):
+    """The route of a grouped convolution of an input of ``xshape`` with a (K, C / groups, R, S) weight; recorded for
+    last_group_route(). "mfma" when the route is switched on and the kernels take the geometry."""
+    route = "direct" if xshape[1] // groups <= 16 else "loop"
+    if gconv_mfma():
+        from . import native
+
+        if native.get().gconv_mfma_supported(xshape[0], xshape[1], xshape[2], xshape[3], wshape[0], wshape[2],
+                                             wshape[3], group_geo(stride, pad, dil, groups)):
+            route = "mfma"
+    _GROUP_ROUTE[0] = route
+    return route
+
+
+def group_transpose_w(w16, groups):
+    """(K, C / G, R, S) channels_last bf16 -> contiguous (C, R, S, K / G): each group's weight transposed for the
+    grouped data-gradient kernel."""
+    K, cin_g, R, S = w16.shape
+    w = w16.permute(0, 2, 3, 1).reshape(groups, K // groups, R, S, cin_g)
+    return w.permute(0, 4, 2, 3, 1).reshape(groups * cin_g, R, S, K // groups).contiguous()
+
+
+def group_wgrad(gy16, x16, wshape, geo, want_db):
+    """fp32 dw (channels_last, shaped like the weight) and db of a grouped convolution: one launch plus the
+    fixed-order sum of its pixel splits."""
+    from . import native
+
+    C = native.get()
+    dw = _zeros(*wshape, device=gy16.device, memory_format=CL)
+    db = _zeros(wshape[0], device=gy16.device) if want_db else None
+    splits = C.gconv_mfma_wgrad_splits(gy16, x16, dw, geo)
+    ws = torch.empty(splits * (dw.numel() + wshape[0]), dtype=torch.float32, device=gy16.device)
+    C.gconv_mfma_wgrad(gy16, x16, dw, db, ws, geo)
+    return dw, db
+
+
+class _GroupConvMfma(torch.autograd.Function):
+    """Grouped convolution on csrc/gconv_mfma.hip: bf16 NHWC operands over all channels, fp32 results, one launch per
+    direction for every group."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, pad, dil, groups):
+        from . import native
+
+        N, C, H, W = x.shape
+        K, cin_g, R, S = w.shape
+        OH, OW = _out_size(H, R, stride[0], pad[0], dil[0]), _out_size(W, S, stride[1], pad[1], dil[1])
+        x16, w16 = _act16(x, C), _w16(w, K, cin_g)
+        geo = group_geo(stride, pad, dil, groups)
+        y = torch.empty((N, K, OH, OW), dtype=torch.float32, device=x.device, memory_format=CL)
+        native.get().gconv_mfma_fwd(x16, w16, b.float().contiguous() if b is not None else None, y, False, geo)
+        ctx.save_for_backward(x16, w16)
+        ctx.geo, ctx.has_b = geo, b is not None
+        return y.contiguous()
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import native
+
+        x16, w16 = ctx.saved_tensors
+        geo = ctx.geo
+        gy16 = _act16(gy, gy.shape[1])
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gi = torch.empty(x16.shape, dtype=torch.float32, device=gy.device, memory_format=CL)
+            native.get().gconv_mfma_dgrad(gy16, group_transpose_w(w16, geo[6]), gi, geo)
+            gx = gi.contiguous()
+        if ctx.needs_input_grad[1] or (ctx.has_b and ctx.needs_input_grad[2]):
+            dw, gb = group_wgrad(gy16, x16, w16.shape, geo, ctx.has_b)
+            gw = dw.contiguous()
+        return gx, gw, gb, None, None, None, None
+
+
 def group_conv2d(x, w, b=None, stride=(1, 1), pad=(0, 0), dil=(1, 1), groups=1):
-    """Grouped convolution: direct kernel when groups carry little reduction depth (depthwise, <= 16 input
-    channels per group), else the implicit-GEMM conv per group writing its channel slice."""
+    """Grouped convolution. With the MFMA route switched on and a geometry it takes (last_group_route() == "mfma"):
+    every group in one launch per direction. Else the direct kernel when groups carry little reduction depth
+    (depthwise, <= 16 input channels per group: "direct"), else the implicit-GEMM conv per group writing its channel
+    slice ("loop")."""
     if not x.is_cuda:
         return F.conv2d(x, w, b, stride, pad, dil, groups)
     if groups == 1:
         return conv2d(x, w, b, stride, pad, dil)
+    route = group_route(x.shape, w.shape, stride, pad, dil, groups)
+    if route == "mfma":
+        return _GroupConvMfma.apply(x, w, b, tuple(stride), tuple(pad), tuple(dil), groups)
     cin_g = x.shape[1] // groups
-    if cin_g <= 16:
+    if route == "direct":
         return _GroupConv.apply(x, w, b, tuple(stride), tuple(pad), tuple(dil), groups)
     cout_g = w.shape[0] // groups
     outs = [conv2d(x[:, g * cin_g:(g + 1) * cin_g], w[g * cout_g:(g + 1) * cout_g],

@@ -195,6 +195,10 @@ class _Engine:
             from ..ops import conv_fn
 
             conv_fn.set_sepconv_fused(v)
+        elif k == "bigdl.gconv.mfma":               # grouped convolution: every group in one MFMA launch per pass
+            from ..ops import conv_fn
+
+            conv_fn.set_gconv_mfma(v)
         elif k == "bigdl.module.deviceTiming":      # getTimes in device time (HIP events) for GPU modules
             from ..nn import abstractnn
 

@@ -2416,6 +2416,88 @@ void conv3d_wgrad(const Tensor& dy, const Tensor& x, const Tensor& dw, const Opt
   TORCH_CHECK(bigdl_conv3d_wgrad(cbf(dy, "dy"), cbf(x, "x"), mf(dw, "dw"), omf(db, "db"), mf(ws, "ws"), &g, stream()) == 0,
               "conv3d_wgrad: unsupported geometry");
 }
+// Grouped convolution on MFMA (csrc/gconv_mfma.hip). x [N][C][H][W] and y / dy [N][K][OH][OW] are channels_last (NHWC
+// memory) tensors over all channels: bf16 as operands, bf16 or fp32 as results (the tensor's dtype picks the kernel's
+// output type); w is bf16 [K][C / G][R][S] channels_last (KRSC memory), wt for the data gradient contiguous bf16
+// [C][R][S][K / G], dw fp32 shaped like w; geo = [sH, sW, pH, pW, dH, dW, G]. Every extent is read from the tensors.
+static GConvMfmaGeo gconv_mfma_geo(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S,
+                                   const std::vector<int64_t>& geo, bool* ok) {
+  TORCH_CHECK(geo.size() == 7, "gconv_mfma: geo = [sH, sW, pH, pW, dH, dW, G]");
+  const int64_t v[] = {N, C, H, W, K, R, S, geo[0], geo[1], geo[2], geo[3], geo[4], geo[5], geo[6]};
+  *ok = R >= 1 && S >= 1 && geo[0] >= 1 && geo[1] >= 1 && geo[4] >= 1 && geo[5] >= 1;
+  for (int64_t e : v) *ok = *ok && e >= 0 && e < (1ll << 31);
+  GConvMfmaGeo g{};
+  if (!*ok) return g;
+  g.N = (int)N; g.C = (int)C; g.H = (int)H; g.W = (int)W; g.K = (int)K; g.R = (int)R; g.S = (int)S;
+  g.sH = (int)geo[0]; g.sW = (int)geo[1]; g.pH = (int)geo[2]; g.pW = (int)geo[3]; g.dH = (int)geo[4]; g.dW = (int)geo[5];
+  g.G = (int)geo[6];
+  const int64_t oh = H + 2 * geo[2] - geo[4] * (R - 1) - 1, ow = W + 2 * geo[3] - geo[5] * (S - 1) - 1;
+  *ok = oh >= 0 && ow >= 0;
+  g.OH = (int)(oh / geo[0] + 1); g.OW = (int)(ow / geo[1] + 1);
+  return g;
+}
+bool gconv_mfma_supported(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S,
+                          std::vector<int64_t> geo) {
+  bool ok;
+  const GConvMfmaGeo g = gconv_mfma_geo(N, C, H, W, K, R, S, geo, &ok);
+  return ok && bigdl_gconv_mfma_supported(&g) == 1;
+}
+static bool nhwc4(const Tensor& t) { return t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast); }
+// the geometry of x -> y with a [K][C / G][R][S]-shaped weight (w or dw), checked against all three tensors
+static GConvMfmaGeo gconv_mfma_args(const Tensor& x, const Tensor& y, int64_t R, int64_t S,
+                                    const std::vector<int64_t>& geo, const char* who) {
+  TORCH_CHECK(nhwc4(x) && nhwc4(y) && x.size(0) == y.size(0), who, ": x / y must be channels_last tensors of one batch");
+  bool ok;
+  const GConvMfmaGeo g = gconv_mfma_geo(x.size(0), x.size(1), x.size(2), x.size(3), y.size(1), R, S, geo, &ok);
+  TORCH_CHECK(ok && bigdl_gconv_mfma_supported(&g) == 1, who, ": unsupported geometry");
+  TORCH_CHECK(y.size(2) == g.OH && y.size(3) == g.OW, who, ": y must be [N][K][OH][OW]");
+  return g;
+}
+static void gconv_mfma_w_check(const Tensor& w, const Tensor& x, const Tensor& y, int64_t G, const char* what) {
+  TORCH_CHECK(nhwc4(w) && G > 0 && w.size(0) == y.size(1) && w.size(1) * G == x.size(1), what);
+}
+static int out16(const Tensor& t, const char* who) {
+  TORCH_CHECK(t.is_cuda() && (t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat), who,
+              ": the output must be a bf16 or fp32 GPU tensor");
+  return t.scalar_type() == at::kBFloat16 ? 1 : 0;
+}
+void gconv_mfma_fwd(const Tensor& x, const Tensor& w, const OptT& bias, const Tensor& y, bool relu,
+                    std::vector<int64_t> geo) {
+  TORCH_CHECK(geo.size() == 7, "gconv_mfma_fwd: geo = [sH, sW, pH, pW, dH, dW, G]");
+  TORCH_CHECK(x.dim() == 4 && y.dim() == 4, "gconv_mfma_fwd: x / y must be 4-D");
+  gconv_mfma_w_check(w, x, y, geo[6], "gconv_mfma_fwd: w must be channels_last [K][C / G][R][S]");
+  const GConvMfmaGeo g = gconv_mfma_args(x, y, w.size(2), w.size(3), geo, "gconv_mfma_fwd");
+  if (bias && bias->defined()) TORCH_CHECK(bias->numel() == g.K && bias->is_contiguous(), "gconv_mfma_fwd: bias is [K]");
+  TORCH_CHECK(bigdl_gconv_mfma_fwd(cbf(x, "x"), cbf(w, "w"), ocf(bias, "bias"), y.data_ptr(), out16(y, "gconv_mfma_fwd"),
+                                   relu ? 1 : 0, &g, stream()) == 0, "gconv_mfma_fwd: launch refused");
+}
+void gconv_mfma_dgrad(const Tensor& dy, const Tensor& wt, const Tensor& dx, std::vector<int64_t> geo) {
+  TORCH_CHECK(geo.size() == 7, "gconv_mfma_dgrad: geo = [sH, sW, pH, pW, dH, dW, G]");
+  TORCH_CHECK(dx.dim() == 4 && dy.dim() == 4, "gconv_mfma_dgrad: dx / dy must be 4-D");
+  TORCH_CHECK(wt.dim() == 4 && wt.is_contiguous() && geo[6] > 0 && wt.size(0) == dx.size(1) &&
+              wt.size(3) * geo[6] == dy.size(1), "gconv_mfma_dgrad: wt must be contiguous [C][R][S][K / G]");
+  const GConvMfmaGeo g = gconv_mfma_args(dx, dy, wt.size(1), wt.size(2), geo, "gconv_mfma_dgrad");
+  TORCH_CHECK(bigdl_gconv_mfma_dgrad(cbf(dy, "dy"), cbf(wt, "wt"), dx.data_ptr(), out16(dx, "gconv_mfma_dgrad"), &g,
+                                     stream()) == 0, "gconv_mfma_dgrad: launch refused");
+}
+// number of pixel splits gconv_mfma_wgrad takes for these tensors (the workspace is splits * (dw.numel() + K) floats)
+int64_t gconv_mfma_wgrad_splits(const Tensor& dy, const Tensor& x, const Tensor& dw, std::vector<int64_t> geo) {
+  TORCH_CHECK(geo.size() == 7, "gconv_mfma_wgrad: geo = [sH, sW, pH, pW, dH, dW, G]");
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4, "gconv_mfma_wgrad: x / dy must be 4-D");
+  gconv_mfma_w_check(dw, x, dy, geo[6], "gconv_mfma_wgrad: dw must be channels_last [K][C / G][R][S]");
+  const GConvMfmaGeo g = gconv_mfma_args(x, dy, dw.size(2), dw.size(3), geo, "gconv_mfma_wgrad");
+  return bigdl_gconv_mfma_wgrad_splits(&g);
+}
+int64_t gconv_mfma_wgrad_split_min() { return bigdl_gconv_mfma_wgrad_split_min(); }
+void gconv_mfma_wgrad(const Tensor& dy, const Tensor& x, const Tensor& dw, const OptT& db, const Tensor& ws,
+                      std::vector<int64_t> geo) {
+  const int64_t splits = gconv_mfma_wgrad_splits(dy, x, dw, geo);
+  const GConvMfmaGeo g = gconv_mfma_args(x, dy, dw.size(2), dw.size(3), geo, "gconv_mfma_wgrad");
+  if (db && db->defined()) TORCH_CHECK(db->numel() == g.K && db->is_contiguous(), "gconv_mfma_wgrad: db is [K]");
+  TORCH_CHECK(ws.is_contiguous() && ws.numel() >= splits * (dw.numel() + g.K), "gconv_mfma_wgrad: workspace too small");
+  TORCH_CHECK(bigdl_gconv_mfma_wgrad(cbf(dy, "dy"), cbf(x, "x"), mf(dw, "dw"), omf(db, "db"), mf(ws, "ws"), &g,
+                                     stream()) == 0, "gconv_mfma_wgrad: launch refused");
+}
 void ones_col_pack(const Tensor& x, const Tensor& xe) {
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && x.size(1) % 8 == 0, "ones_col_pack: x must be [M, K] contiguous, K % 8 == 0");
   TORCH_CHECK(xe.dim() == 2 && xe.is_contiguous() && xe.size(0) == x.size(0) && xe.size(1) == x.size(1) + 8,
@@ -2682,6 +2764,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gconv", &gconv);
   m.def("sepconv_fwd", &sepconv_fwd);
   m.def("sepconv_supported", &sepconv_supported);
+  m.def("gconv_mfma_supported", &gconv_mfma_supported);
+  m.def("gconv_mfma_fwd", &gconv_mfma_fwd);
+  m.def("gconv_mfma_dgrad", &gconv_mfma_dgrad);
+  m.def("gconv_mfma_wgrad", &gconv_mfma_wgrad);
+  m.def("gconv_mfma_wgrad_splits", &gconv_mfma_wgrad_splits);
+  m.def("gconv_mfma_wgrad_split_min", &gconv_mfma_wgrad_split_min);
   m.def("conv3d_fwd", &conv3d_fwd);
   m.def("conv3d_dgrad", &conv3d_dgrad);
   m.def("conv3d_wgrad", &conv3d_wgrad);

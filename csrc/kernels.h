@@ -826,4 +826,28 @@ typedef struct { int N, Cin, dm, H, W, Cout, OH, OW, kH, kW, sH, sW, pH, pW; } S
 int bigdl_sepconv_supported(const SepConvGeo* g);
 int bigdl_sepconv_fwd(const float* x, const float* wd, const uint16_t* wp, const float* bias, float* y,
                       uint16_t* mid16, const SepConvGeo* g, hipStream_t st);
+
+// Grouped convolution on MFMA (csrc/gconv_mfma.hip): every group in one launch per direction. The geometry is that of
+// the convolution x[N][H][W][C] (*) w -> y[N][OH][OW][K] with G groups whichever direction runs: bf16 NHWC activations
+// over all channels, w bf16 [K][R][S][C / G]. bigdl_gconv_mfma_supported: 1 when the kernels take the geometry (G >= 2,
+// C / G and K / G multiples of 8, strides and dilations >= 1, 0 <= pad < dilated kernel extent, OH / OW the
+// convolution's output size, every tensor below 2^31 elements); the launch entries return -1 otherwise.
+typedef struct { int N, H, W, C, OH, OW, K, G, R, S, sH, sW, pH, pW, dH, dW; } GConvMfmaGeo;
+int bigdl_gconv_mfma_supported(const GConvMfmaGeo* g);
+// y = [relu](x (*) w + bias): y bf16 (out_bf16) or fp32 [N][OH][OW][K]; bias fp32 [K] or null
+int bigdl_gconv_mfma_fwd(const uint16_t* x, const uint16_t* w, const float* bias, void* y, int out_bf16, int relu,
+                         const GConvMfmaGeo* g, hipStream_t st);
+// dx = dy (*)^T w (every element of dx is written): wt bf16 [C][R][S][K / G], the per-group transpose of w
+// (wt[g cin_g + c][r][s][k] = w[g cout_g + k][r][s][c]); dx bf16 (out_bf16) or fp32 [N][H][W][C]
+int bigdl_gconv_mfma_dgrad(const uint16_t* dy, const uint16_t* wt, void* dx, int out_bf16, const GConvMfmaGeo* g,
+                           hipStream_t st);
+// The weight gradient ACCUMULATES: dw[K][R][S][C / G] += dy^T x, db[K] += column sums of dy (db may be null), both fp32;
+// a caller that wants the gradient alone passes zeros. ws: fp32 workspace of bigdl_gconv_mfma_wgrad_splits(g) *
+// (K * R * S * C / G + K) floats, no need to clear it. The pixels are split once there are at least
+// bigdl_gconv_mfma_wgrad_split_min() of them and the tiles alone leave the chip short; the splits are summed in fixed
+// order by bigdl_split_reduce_f32, so two launches give the same bits.
+int bigdl_gconv_mfma_wgrad_splits(const GConvMfmaGeo* g);
+int bigdl_gconv_mfma_wgrad_split_min(void);
+int bigdl_gconv_mfma_wgrad(const uint16_t* dy, const uint16_t* x, float* dw, float* db, float* ws,
+                           const GConvMfmaGeo* g, hipStream_t st);
 }
